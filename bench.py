@@ -1,8 +1,14 @@
 """Benchmark: Msamples/s (forward) + grad-Msamples/s (adjoint), 512x512 Cornell
 box, 64 spp, 4 bounces (BASELINE.json configs[1]) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K forward steps of the headline,
+writes the last step's image if --dump-outputs is given, and prints the result
+line.  Everything else below (the adjoint leg, the one-stream pass and the
+roofline it feeds, the in-flight-equals-alone checks, the secondary lines and
+the CPU baseline) runs only with --full.
 
 A step is one C2 frame, tiled across the ranks exactly as the north_star asks
 ("image tiles shard across the GPUs, RCCL reduce on the per-material gradient
@@ -131,6 +137,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the adjoint leg, the one-stream "
+                         "pass and roofline, in-flight-equals-alone checks, secondary lines, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the HDR image the last timed forward step produced to "
+                         "DIR/hdr.npy (float32, this rank's rows x width x 3; DIR/hdr_rank<r>.npy on N > 1 ranks)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary lines (profiling runs: keeps the C2 kernel's statistics pure)")
@@ -424,6 +436,42 @@ def graph_line(cx, seed=0, reps=5):
     return out
 
 
+def dump_outputs(directory, head, steps, world, rank):
+    """The HDR image of the last timed (in-flight) forward step, as its caller
+    receives it: this rank's rows of the frame, float32.  Call after the timed
+    region has drained and before anything renders into the same buffer."""
+    os.makedirs(directory, exist_ok=True)
+    img = head.hdr2[(steps - 1) % len(head.streams)].cpu().numpy().reshape(head.rows, head.w, 3)
+    np.save(os.path.join(directory, "hdr.npy" if world == 1 else "hdr_rank%d.npy" % rank), img)
+
+
+def headline(args, world, head, fwd_ms, wall_fwd, rows):
+    """The result line's fields that every run measures."""
+    return {
+        "metric": "Msamples/sec fwd + grad-Msamples/sec, 512² Cornell 64spp, 1/2/4/8 GPU",
+        "value": round(args.steps * W * H * SPP / (fwd_ms / 1e3) / 1e6, 2), "unit": "Msamples/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(fwd_ms / args.steps, 4),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "full": args.full,
+        "config": {"workload": "C2: CornellBox-Empty-CO.obj, 512x512, 64 spp, max_bounces=4; one frame per step "
+                               "tiled over the ranks as interleaved rows (fwd); adjoint dL/dKd of the rank's rows "
+                               "+ RCCL all-reduce of the gradient (grad, --full); %d frames in flight (consecutive "
+                               "steps round-robin over %d HIP streams; one stream: secondary.serial)"
+                               % (NSTREAMS, NSTREAMS),
+                   "streams": NSTREAMS,
+                   "width": W, "height": H, "spp": SPP, "max_bounces": BOUNCES, "triangles": head.sc.nT,
+                   "parallelism": "interleaved row tiles x%d" % world, "rank0_rows": list(rows)},
+        "wall_s_fwd_region": round(wall_fwd, 4),
+    }
+
+
+def finish(head, world):
+    head.close()
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -449,6 +497,17 @@ def main():
         head.adjoint(10**6 + i)
         head.fwd(10**6 + i, piped=True)
         head.adjoint(10**6 + i, piped=True)
+    if not args.full:
+        # the plain run: the headline's K forward steps (frames in flight) and nothing else
+        t_wall = time.perf_counter()
+        fwd_ms = cx.timed(lambda i: head.fwd(i, piped=True), args.steps, head.streams)
+        wall_fwd = time.perf_counter() - t_wall
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, head, args.steps, world, rank)
+        if rank == 0:
+            print(json.dumps(headline(args, world, head, fwd_ms, wall_fwd, (b, e, rs))), flush=True)
+        finish(head, world)
+        return
     # ---------------------------------------------------------- headline: tile-split C2 frame
     # (1) frames one after another on one stream: each launch's own time
     # (HIP events around it: the roofline's kernel time) and the serial rate
@@ -462,6 +521,8 @@ def main():
     t_wall = time.perf_counter()
     fwd_ms = cx.timed(lambda i: head.fwd(i, piped=True), args.steps, head.streams)
     wall_fwd = time.perf_counter() - t_wall
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, head, args.steps, world, rank)
     # the last NSTREAMS frames in flight, re-rendered alone: bitwise the same images
     last = list(range(max(0, args.steps - len(head.streams)), args.steps))
     got = {i: head.hdr2[i % len(head.streams)].clone() for i in last}  # (hdr2[0] is head.hdr, which fwd(i) overwrites)
@@ -492,7 +553,6 @@ def main():
         print("bench: adjoints in flight differ from adjoints alone: %s" % adj_ok, file=sys.stderr)
         bwd_ms = bwd_serial_ms
     frame = W * H * SPP
-    value = args.steps * frame / (fwd_ms / 1e3) / 1e6
     grad_value = args.steps * frame / (bwd_ms / 1e3) / 1e6
 
     extra = {"serial": {"value": round(args.steps * frame / (fwd_serial_ms / 1e3) / 1e6, 2),
@@ -638,28 +698,15 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
     if rank == 0:
-        out = {
-            "metric": "Msamples/sec fwd + grad-Msamples/sec, 512² Cornell 64spp, 1/2/4/8 GPU",
-            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(fwd_ms / args.steps, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "C2: CornellBox-Empty-CO.obj, 512x512, 64 spp, max_bounces=4; one frame per step "
-                                   "tiled over the ranks as interleaved rows (fwd); adjoint dL/dKd of the rank's rows "
-                                   "+ RCCL all-reduce of the gradient (grad); %d frames in flight (consecutive steps "
-                                   "round-robin over %d HIP streams; one stream: secondary.serial)" % (NSTREAMS, NSTREAMS),
-                       "streams": NSTREAMS if piped_adj else "%d (fwd) / 1 (grad: gloo)" % NSTREAMS,
-                       "width": W, "height": H, "spp": SPP, "max_bounces": BOUNCES, "triangles": head.sc.nT,
-                       "parallelism": "interleaved row tiles x%d" % world, "rank0_rows": [b, e, rs]},
+        out = headline(args, world, head, fwd_ms, wall_fwd, (b, e, rs))
+        out["config"]["streams"] = NSTREAMS if piped_adj else "%d (fwd) / 1 (grad: gloo)" % NSTREAMS
+        out.update({
             "grad_value": round(grad_value, 2), "grad_unit": "grad-Msamples/s",
             "grad_ms_per_step": round(bwd_ms / args.steps, 4),
-            "wall_s_fwd_region": round(wall_fwd, 4),
             "roofline": roofline, "hbm": hbm, "cpu_baseline": cpu, "secondary": extra,
-        }
+        })
         print(json.dumps(out), flush=True)
-    head.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(head, world)
 
 
 if __name__ == "__main__":

@@ -8,11 +8,11 @@
 # Stages:
 #   smoke        __graft_entry__.smoke()
 #   tests        pytest -m gpu ($TESTS, default tests; $PYTEST_K for -k)
-#   bench        bench.py (full JSON line)
-#   benchq       bench.py --no-secondary --no-cpu-baseline
+#   bench        bench.py --full (the JSON line with every secondary figure)
+#   benchq       bench.py --full --no-secondary --no-cpu-baseline (headline, adjoint leg, one-stream pass, checks)
 #   benchd       bench.py exactly as the driver runs it (--gpus 1 --steps 20 --warmup 5)
 #   benchrep     the driver's form three times back to back (run-to-run spread in one box)
-#   benchsteps   headline only (--no-secondary --no-cpu-baseline) at 20 / 60 / 200 steps, warmup 5
+#   benchsteps   headline legs only (--full --no-secondary --no-cpu-baseline) at 20 / 60 / 200 steps, warmup 5
 #   prof         rocprofv3 --kernel-trace --stats of the C2 headline (no secondary lines)
 #   pmc          FETCH_SIZE / WRITE_SIZE passes of the C2 headline (separate runs)
 #   sq           SQ counter passes of the C2 headline
@@ -29,7 +29,7 @@
 #   variants     tools/variant_bench.py $VARIANTS ($VB_ONLY scenes; IPT_VB_* passed through)
 #   phase        tools/phase_timing.py
 #   stats        tools/bvh_stats.py with the IPT_BVH_STATS variant library ($SCENES)
-#   multirank    2-rank gloo rehearsal of bench.py on the one GPU
+#   multirank    2-rank gloo rehearsal of bench.py --full on the one GPU
 #   scaling      tools/launch_scaling.py (fixed cost per launch: C2 shares 1/1 .. 1/64)
 #   workflow     tools/workflow_at_size.py (pipeline all --n 100 + optimize --n 100)
 #   graphprof    rocprofv3 --kernel-trace --stats of createGraph at the reference config (tools/graph_prof.py)
@@ -68,7 +68,7 @@ TCP_TCC_ATOMIC_WITH_RET_REQ_sum TCP_TCC_ATOMIC_WITHOUT_RET_REQ_sum TCP_TCC_READ_
 TCC_HIT_sum TCC_MISS_sum"
 MIX_SETS="SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64
 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_MFMA_F32 SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM"
-BENCHQ=(python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-secondary)
+BENCHQ=(python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary)
 NS=(python3 "$R/tools/bench_scenes.py" --scenes northstar --brute-max-tris 0)
 UP=(python3 "$R/tools/unbounded_prof.py")
 
@@ -77,19 +77,19 @@ run() {
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$T.log" 2>&1 ;;
     tests) timeout -k 10 1000 python -u -m pytest ${TESTS:-tests} -m gpu -v --maxfail=5 --timeout 300 \
                --timeout-method thread -p no:cacheprovider ${PYTEST_K:+-k "$PYTEST_K"} > "$OUT/pytest_gpu_$T.log" 2>&1 ;;
-    bench) timeout -k 10 600 python bench.py > "$OUT/bench_$T.json" 2> "$OUT/bench_$T.err" ;;
+    bench) timeout -k 10 600 python bench.py --full > "$OUT/bench_$T.json" 2> "$OUT/bench_$T.err" ;;
     benchd) timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/benchd_$T.json" 2> "$OUT/benchd_$T.err" ;;
     benchsteps) for k in 20 60 200 20; do
-                  timeout -k 10 300 python3 bench.py --steps $k --warmup 5 --no-secondary --no-cpu-baseline \
+                  timeout -k 10 300 python3 bench.py --full --steps $k --warmup 5 --no-secondary --no-cpu-baseline \
                       >> "$OUT/benchsteps_$T.jsonl" 2>> "$OUT/benchsteps_$T.err" || return 1
                 done ;;
     benchrep) for k in 1 2 3; do
                 timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/benchrep_${T}_$k.json" \
                     2> "$OUT/benchrep_${T}_$k.err" || return 1
               done ;;
-    benchq) timeout -k 10 300 python bench.py --no-secondary --no-cpu-baseline > "$OUT/benchq_$T.json" 2> "$OUT/benchq_$T.err" ;;
+    benchq) timeout -k 10 300 python bench.py --full --no-secondary --no-cpu-baseline > "$OUT/benchq_$T.json" 2> "$OUT/benchq_$T.err" ;;
     prof) timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$T" -o run --output-format csv \
-              -- python3 "$R/bench.py" --steps 20 --warmup 2 --no-cpu-baseline --no-secondary > "$OUT/prof_$T.log" 2>&1 ;;
+              -- python3 "$R/bench.py" --full --steps 20 --warmup 2 --no-cpu-baseline --no-secondary > "$OUT/prof_$T.log" 2>&1 ;;
     pmc) SETS=$'FETCH_SIZE\nWRITE_SIZE' pmc_passes pmc "${BENCHQ[@]}" ;;
     sq) SETS=$SQ_SETS pmc_passes sq "${BENCHQ[@]}" ;;
     attr) SETS=$ATTR_SETS pmc_passes attr "${BENCHQ[@]}" ;;
@@ -112,7 +112,7 @@ run() {
     stats) IPT_AMD_LIB=$R/inverse_path_tracer_amd/lib/variants/libipt_stats.so timeout -k 10 300 \
                python tools/bvh_stats.py ${SCENES:+--scenes $SCENES} --out "$OUT/stats_$T.json" > "$OUT/stats_$T.log" 2>&1 ;;
     multirank) IPT_BENCH_DEVICE=0 IPT_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
-                   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 40 \
+                   --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 40 \
                    --warmup 4 > "$OUT/bench_2rank_$T.json" 2> "$OUT/bench_2rank_$T.err" ;;
     scaling) timeout -k 10 300 python tools/launch_scaling.py > "$OUT/scaling_$T.jsonl" 2> "$OUT/scaling_$T.err" ;;
     workflow) timeout -k 10 1000 python -u tools/workflow_at_size.py --out "$OUT/workflow_$T.json" > "$OUT/workflow_$T.log" 2>&1 ;;

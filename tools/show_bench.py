@@ -1,4 +1,4 @@
-"""Summarise a bench.py JSON line (last line of the file given)."""
+"""Summarise a `bench.py --full` JSON line (last line of the file given)."""
 import json
 import sys
 
