@@ -216,6 +216,32 @@ int ipt_render_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint6
 int ipt_adjoint_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride, const float *kd_dev,
                           const float *adj_dev, double *grad_dev, void *stream);
 
+/* Material parameters beyond Kd: specular Ks (with its Phong exponent Ns)
+ * and emission Ke, per triangle.  STRUCTURE IS FROZEN AT LOAD: which
+ * triangles are emitters (the emitter list, cdf and pmf) and which carry a
+ * Phong lobe (and its exponent) are decided by the MTL files; these entry
+ * points change values only.  Ke rows of non-emitters and Ks rows of
+ * lobe-less triangles are ignored and stay 0, and their gradient rows are
+ * exactly 0.  An emitter or lobe triangle may be given all-zero values (the
+ * kernels branch on the load-time flags).  Ns is not differentiated.
+ * (Additive symbols: ipt_abi_version stays 5.)
+ *
+ * get/set: host arrays, nT*3 floats each (ns: nT), each nullable; set
+ * re-uploads the scene's tables and leaves setMaterials' behaviour as is. */
+int ipt_scene_get_material_params(void *scene, float *kd, float *ks, float *ke, float *ns);
+int ipt_scene_set_material_params(void *scene, const float *kd, const float *ks, const float *ke);
+/* ipt_render_dev with per-launch overrides: kd_dev / ks_dev / ke_dev are
+ * device arrays of nT*3 floats, NULL = the scene's own. */
+int ipt_render_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                       const float *ke_dev, float *hdr_dev, uint8_t *ldr_dev, void *stream);
+/* d(sum adj*I)/d(Kd, Ks, Ke) of the bounded estimator in one launch:
+ * grad_dev is 3*nT*3 doubles, [Kd | Ks | Ke], ACCUMULATED (zero it first).
+ * The Kd block equals ipt_adjoint_dev's.  Refused with an error:
+ * max_bounces < 0 (the unbounded estimator) and max_bounces > 62. */
+int ipt_adjoint_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                        const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
+int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj /*H*W*3*/, double *grad /*3*nT*3*/);
+
 /* PNG helpers (RGB8). ipt_png_read with rgb == NULL only reports the size. */
 int ipt_png_write(const char *path, int width, int height, const uint8_t *rgb);
 int ipt_png_read(const char *path, int *width, int *height, uint8_t *rgb, int64_t capacity);

@@ -294,6 +294,36 @@ int ipt_scene_set_materials(void *scene, const float *kd) {
   return gpu_status(ipt::gpu_set_kd(s, kd));
 }
 
+int ipt_scene_get_material_params(void *scene, float *kd, float *ks, float *ke, float *ns) {
+  GpuScene *s = as_scene(scene);
+  if (!s) return -1;
+  const ipt::HostScene &h = ipt::gpu_host(s);
+  if (kd) std::memcpy(kd, h.kd.data(), h.kd.size() * sizeof(float));
+  for (int i = 0; i < h.nT; ++i) {
+    const ipt::TriMat &m = h.mat[(size_t)i];
+    for (int c = 0; c < 3; ++c) {
+      if (ks) ks[3 * i + c] = m.ks[c];
+      if (ke) ke[3 * i + c] = m.ke[c];
+    }
+    if (ns) ns[i] = m.shininess;
+  }
+  return 0;
+}
+int ipt_scene_set_material_params(void *scene, const float *kd, const float *ks, const float *ke) {
+  GpuScene *s = as_scene(scene);
+  if (!s) return -1;
+  const size_t n = (size_t)ipt::gpu_host(s).nT * 3;
+  const float *arr[3] = {kd, ks, ke};
+  const char *name[3] = {"kd", "ks", "ke"};
+  for (int k = 0; k < 3; ++k)
+    for (size_t i = 0; arr[k] && i < n; ++i)
+      if (!std::isfinite(arr[k][i])) {
+        fail(std::string("ipt_scene_set_material_params: ") + name[k] + " holds a non-finite value");
+        return -1;
+      }
+  return gpu_status(ipt::gpu_set_material_params(s, kd, ks, ke));
+}
+
 void getMaterials(void *scenePtr, float *materials) {
   GpuScene *s = as_scene(scenePtr);
   if (!s || !materials) return;
@@ -420,6 +450,35 @@ int ipt_adjoint_dev(void *scene, const ipt_params_t *p, const float *kd_dev, con
   GpuScene *s = as_scene(scene);
   if (!s || !p || !adj_dev || !grad_dev) return -1;
   return gpu_status(ipt::gpu_adjoint(s, to_params(p), kd_dev, adj_dev, grad_dev, stream));
+}
+
+int ipt_render_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                       const float *ke_dev, float *hdr_dev, uint8_t *ldr_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !hdr_dev) {
+    if (s) fail("ipt_render_mat_dev: bad arguments (params and hdr_dev are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_render_mat(s, to_params(p), kd_dev, ks_dev, ke_dev, hdr_dev, ldr_dev, stream));
+}
+
+int ipt_adjoint_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                        const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !adj_dev || !grad_dev) {
+    if (s) fail("ipt_adjoint_mat_dev: bad arguments (params, adj_dev and grad_dev are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_adjoint_mat(s, to_params(p), kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream));
+}
+
+int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj, double *grad) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !adj || !grad) {
+    if (s) fail("ipt_adjoint_mat_host: bad arguments (params, adj and grad are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_adjoint_mat_host(s, to_params(p), adj, grad));
 }
 
 int ipt_render_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride, const float *kd_dev,

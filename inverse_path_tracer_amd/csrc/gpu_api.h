@@ -39,6 +39,19 @@ int gpu_adjoint(GpuScene *s, const RenderParams &p, const float *kd_dev, const f
                 double *grad_dev, void *stream);
 int gpu_graph(GpuScene *s, const RenderParams &p, const uint8_t *target_dev, double *acc_dev, void *stream);
 
+// Material parameters beyond Kd.  Structure is frozen at load: the emitter
+// list and the lobe flags stay, values change; Ke rows of non-emitters and Ks
+// rows of lobe-less triangles are forced to 0.  Host arrays nT*3, nullable.
+int gpu_set_material_params(GpuScene *s, const float *kd, const float *ks, const float *ke);
+// Forward with per-launch overrides (device arrays nT*3; nullptr = the scene's own).
+int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
+                   float *hdr_dev, uint8_t *ldr_dev, void *stream);
+// Bounded adjoint in Kd, Ks and Ke: grad_dev is 3 x nT x 3 doubles [Kd | Ks | Ke], accumulated.
+// Refuses max_bounces < 0 and the scene batch.
+int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
+                    const float *adj_dev, double *grad_dev, void *stream);
+int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad);
+
 // Host-memory conveniences (allocate, copy, run, copy back, synchronize).
 int gpu_render_samples_host(GpuScene *s, const RenderParams &p, float *samples);
 int gpu_render_host(GpuScene *s, const RenderParams &p, float *hdr, uint8_t *ldr);

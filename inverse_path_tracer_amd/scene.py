@@ -111,6 +111,8 @@ class Scene:
         self.handle = h
         self.nT = nT
         self.nE = L.ipt_scene_num_emissives(h)
+        # the lobe flags are fixed here, from the MTL values (a later set_material_params may zero a lobe's Ks)
+        self._lobe_mask = (self.material_params()[1] != 0).any(axis=1)
 
     @classmethod
     def from_file(cls, path: str, root: Optional[str] = None, device: bool = True) -> "Scene":
@@ -147,6 +149,35 @@ class Scene:
     def materials(self, kd):
         kd = np.ascontiguousarray(np.asarray(kd, np.float32).reshape(self.nT, 3))
         N.check(N.lib().ipt_scene_set_materials(self.handle, kd.ctypes.data_as(N.fp)), "setMaterials")
+
+    def material_params(self):
+        """(kd, ks, ke, ns): per-triangle diffuse, specular and emitted colour,
+        (nT, 3) float32 each, and the Phong exponent (nT,)."""
+        kd, ks, ke = (np.zeros((self.nT, 3), np.float32) for _ in range(3))
+        ns = np.zeros(self.nT, np.float32)
+        N.check(N.lib().ipt_scene_get_material_params(self.handle, kd.ctypes.data_as(N.fp), ks.ctypes.data_as(N.fp),
+                                                      ke.ctypes.data_as(N.fp), ns.ctypes.data_as(N.fp)),
+                "get_material_params")
+        return kd, ks, ke, ns
+
+    def set_material_params(self, kd=None, ks=None, ke=None):
+        """Replace material VALUES (None: keep).  Structure is frozen at load:
+        ke rows outside emitter_mask and ks rows outside lobe_mask are ignored
+        and stay 0."""
+        arrs = [None if v is None else np.ascontiguousarray(np.asarray(v, np.float32).reshape(self.nT, 3))
+                for v in (kd, ks, ke)]
+        ptrs = [None if a is None else a.ctypes.data_as(N.fp) for a in arrs]
+        N.check(N.lib().ipt_scene_set_material_params(self.handle, *ptrs), "set_material_params")
+
+    @property
+    def emitter_mask(self) -> np.ndarray:
+        """bool (nT,): the triangles on the emitter list built at load (the only rows Ke acts on)."""
+        return self.triangles()[:, 56] >= 0
+
+    @property
+    def lobe_mask(self) -> np.ndarray:
+        """bool (nT,): the triangles that carried a Phong lobe (Ks != 0) at load (the only rows Ks acts on)."""
+        return self._lobe_mask.copy()
 
     def triangles(self) -> np.ndarray:
         out = np.zeros((self.nT, N.TRI_EXPORT_STRIDE), np.float32)
@@ -256,6 +287,18 @@ class Scene:
         N.check(N.lib().ipt_adjoint_host(self.handle, C.byref(p), adj.ctypes.data_as(N.fp),
                                          g.ctypes.data_as(N.dp)), "adjoint")
         return g
+
+    def adjoint_materials(self, adj, width, height, spp, max_bounces, seed=0, row_begin=0, row_end=None, row_step=1):
+        """d(sum(adj * I))/d(Kd, Ks, Ke) as three (nT, 3) float64 arrays, from
+        one launch of the material adjoint (bounded estimator only:
+        max_bounces None is refused).  Rows of Ks outside lobe_mask and of Ke
+        outside emitter_mask are exactly 0."""
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        adj = np.ascontiguousarray(np.asarray(adj, np.float32).reshape(height, width, 3))
+        g = np.zeros((3, self.nT, 3), np.float64)
+        N.check(N.lib().ipt_adjoint_mat_host(self.handle, C.byref(p), adj.ctypes.data_as(N.fp),
+                                             g.ctypes.data_as(N.dp)), "adjoint_materials")
+        return g[0], g[1], g[2]
 
     def graph(self, target, width, height, spp, max_bounces=None, seed=0, row_begin=0, row_end=None, row_step=1):
         """createGraph: returns (acc[(nT+1)*nT, 8] float64, data[(nT+1)*nT*7] float32)."""

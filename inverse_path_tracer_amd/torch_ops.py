@@ -100,6 +100,69 @@ def render(scene: Scene, kd: torch.Tensor, width: int, height: int, spp: int, ma
     return _RenderFn.apply(kd, scene, p, adjoint_seed)
 
 
+BATCH_REFUSED = "material adjoint: the scene batch (n_scenes > 1) is not supported"
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+class _RenderMaterialsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kd, ks, ke, scene, params, adjoint_seed):
+        dev = next(t for t in (kd, ks, ke) if t is not None).device
+        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
+        hdr = torch.empty((params.rows, params.width, 3), device=dev, dtype=torch.float32)
+        N.check(N.lib().ipt_render_mat_dev(scene.handle, C.byref(params), _ptr(c[0]), _ptr(c[1]), _ptr(c[2]),
+                                           hdr.data_ptr(), None, _stream(dev)), "ipt_render_mat_dev")
+        ctx.scene, ctx.params, ctx.adjoint_seed, ctx.mat = scene, params, adjoint_seed, c
+        return hdr
+
+    @staticmethod
+    def backward(ctx, grad_hdr):
+        p = _replay_params(ctx.params, ctx.adjoint_seed)
+        kd, ks, ke = ctx.mat
+        adj = grad_hdr.float().contiguous()
+        g = torch.zeros((3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
+        if p.row_step > 1:  # interleaved rows: scatter into a full-frame image (as adjoint_band)
+            full = torch.zeros((p.height, p.width, 3), device=adj.device, dtype=torch.float32)
+            full[p.row_begin:p.row_end:p.row_step] = adj
+            base = full.data_ptr()
+        else:
+            base = adj.data_ptr() - p.row_begin * p.width * 3 * 4  # global-pixel indexing
+        N.check(N.lib().ipt_adjoint_mat_dev(ctx.scene.handle, C.byref(p), _ptr(kd), _ptr(ks), _ptr(ke), base,
+                                            g.data_ptr(), _stream(adj.device)), "ipt_adjoint_mat_dev")
+        out = [g[i].float() if (t is not None and ctx.needs_input_grad[i]) else None
+               for i, t in enumerate((kd, ks, ke))]
+        return out[0], out[1], out[2], None, None, None
+
+
+def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4, seed: int = 0,
+                     row_begin: int = 0, row_end=None, adjoint_seed=None, row_step: int = 1) -> torch.Tensor:
+    """Differentiable render w.r.t. diffuse kd, specular ks and emission ke
+    ((nT, 3) CUDA tensors; any may be None = the scene's own values, or not
+    require grad).  The forward is ``render``'s with the overrides; the
+    backward is ONE launch of the material adjoint.  Structure is frozen at
+    load: ke rows outside ``scene.emitter_mask`` and ks rows outside
+    ``scene.lobe_mask`` are ignored, and their gradients are exactly 0; the
+    Phong exponent is not differentiated.  Refused (NativeError): the
+    unbounded estimator (max_bounces None) and batched inputs (S, nT, 3).
+    `adjoint_seed` as in ``render``."""
+    given = [t for t in (kd, ks, ke) if t is not None]
+    if not given:
+        raise ValueError("render_materials needs at least one of kd, ks, ke as a device tensor")
+    for t in given:
+        if t.dim() == 3:
+            raise N.NativeError(BATCH_REFUSED)
+        if tuple(t.shape) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+    if max_bounces is None or max_bounces < 0:
+        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; "
+                            "give max_bounces in 0..62")
+    p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+    return _RenderMaterialsFn.apply(kd, ks, ke, scene, p, adjoint_seed)
+
+
 class _BatchRenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, kd, scene, params, stride, adjoint_seed):
