@@ -703,10 +703,172 @@ __device__ __forceinline__ TriPair load_pair_lds(const lds_f32 *pl, int j) {
   }
   return T;
 }
+// IPT_SHADOW_PAIR1=1: one evaluation of the target's pair
+// decides the target (its half: hit_test's conditions with bt = inf) and its
+// partner (the other half, under occlusion_pass's bound), instead of
+// hit_test on the target's TriIsect record followed by pair_occludes on the
+// pair that holds it; and the cull setup (slab_ray, box bits, the pair loop)
+// is skipped by the wave when no live lane has another pair to test.
+// 0 keeps the two-step route and its LDS copy of the TriIsect array.
+// IPT_SHADOW_PAIR1_SRC: where the pair comes from.  1: scalar loads of
+// pairs[j] when a ballot shows every lane aims at the same pair (one emitter
+// quad), else per lane, half by half, from the workgroup's LDS copy of the
+// pairs (IPT_PATH_CULL's; global memory without it); 0: always per lane, the
+// whole pair gathered from the LDS copy (36 VGPRs: every brute-force instance
+// then spills).
+#ifndef IPT_SHADOW_PAIR1
+#define IPT_SHADOW_PAIR1 1
+#endif
+#ifndef IPT_PATH_CULL
+#define IPT_PATH_CULL 1
+#endif
+#ifndef IPT_SHADOW_PAIR1_SRC
+#define IPT_SHADOW_PAIR1_SRC 1
+#endif
+#if !IPT_PATH_CULL && !IPT_SHADOW_PAIR1_SRC
+#error "IPT_SHADOW_PAIR1_SRC=0 reads the LDS pair copy that only IPT_PATH_CULL=1 stages"
+#endif
+// LDS floats per triangle of the TriIsect copy (the two-step route's only)
+constexpr int kIsectLdsFloats = IPT_SHADOW_PAIR1 ? 0 : 20;
+
+// hit_test's arithmetic on one half of a pair (triangle i = 2j + h is
+// TriPair j's f[k][h]) without the best-t condition: t and "accepts".  The
+// record comes per lane from the workgroup's LDS copy of the pairs, or from
+// global memory when there is none (IPT_PATH_CULL=0).
+__device__ __forceinline__ bool half_test(const lds_f32 *pl, const TriPair *pg, int i, V3 p, V3 d, float &t) {
+  float f[18];
+#if IPT_PATH_CULL
+  const lds_f32 *q = pl + 36 * (i >> 1) + (i & 1);
+#else
+  const float *q = reinterpret_cast<const float *>(pg) + 36 * (i >> 1) + (i & 1);
+#endif
+#pragma unroll
+  for (int k = 0; k < 18; ++k) f[k] = q[2 * k];
+  const float denom = fmaf(f[5], d.z, fmaf(f[4], d.y, f[3] * d.x));
+  const float px = p.x - f[0], py = p.y - f[1], pz = p.z - f[2];
+  const float num = fmaf(pz, f[5], fmaf(py, f[4], px * f[3]));
+  t = div_inrange(num, -denom);
+  const float qx = fmaf(d.x, t, p.x), qy = fmaf(d.y, t, p.y), qz = fmaf(d.z, t, p.z);
+  const float s0 = fmaf(qz, f[8], fmaf(qy, f[7], fmaf(qx, f[6], f[9])));
+  const float s1 = fmaf(qz, f[12], fmaf(qy, f[11], fmaf(qx, f[10], f[13])));
+  const float s2 = fmaf(qz, f[16], fmaf(qy, f[15], fmaf(qx, f[14], f[17])));
+  return !(fabsf(denom) < kMinDotUp) && !(t < kEpsUp) && !(s0 > 0.f) && !(s1 > 0.f) && !(s2 > 0.f);
+}
+
+// pair_ray's arithmetic on the pair that holds the shadow target (half
+// `odd`).  The target accepts under hit_test's conditions from the empty
+// state (the accept tests and !(t >= inf)); te = its t, or inf when it does
+// not.  The partner occludes when it accepts with t < te, or t <= te when its
+// index is the lower one (odd: the partner is the first half) --
+// occlusion_pass's rule.  Returns "accepted and not occluded by the partner".
+__device__ __forceinline__ bool pair_target(const TriPair &T, const PairOrigin &o, int odd, V3 p, V3 d, f2 e03,
+                                            f2 e13, f2 e23, float &te) {
+  const f2 n0 = ld2(T, 3), n1 = ld2(T, 4), n2 = ld2(T, 5);
+  const f2 denom = fma2(n2, bc2(d.z), fma2(n1, bc2(d.y), n0 * bc2(d.x)));
+  const f2 num = o.num;
+#if IPT_FASTDIV
+  const f2 nb = denom;
+  const f2 r0 = f2{__builtin_amdgcn_rcpf(-denom.x), __builtin_amdgcn_rcpf(-denom.y)};
+  const f2 e0 = fma2(nb, r0, bc2(1.0f));
+  const f2 r1 = fma2(e0, r0, r0);
+  const f2 q0 = num * r1;
+  const f2 e1 = fma2(nb, q0, num);
+  const f2 q1 = fma2(e1, r1, q0);
+  const f2 e2 = fma2(nb, q1, num);
+  const f2 t = fma2(e2, r1, q1);  // == div_inrange(num, -denom) per half
+#else
+  const f2 t = f2{num.x / -denom.x, num.y / -denom.y};
+#endif
+  const f2 qx = fma2(bc2(d.x), t, bc2(p.x)), qy = fma2(bc2(d.y), t, bc2(p.y)), qz = fma2(bc2(d.z), t, bc2(p.z));
+  const f2 s0 = fma2(qz, ld2(T, 8), fma2(qy, ld2(T, 7), fma2(qx, ld2(T, 6), e03)));
+  const f2 s1 = fma2(qz, ld2(T, 12), fma2(qy, ld2(T, 11), fma2(qx, ld2(T, 10), e13)));
+  const f2 s2 = fma2(qz, ld2(T, 16), fma2(qy, ld2(T, 15), fma2(qx, ld2(T, 14), e23)));
+  const bool va = !(fabsf(denom.x) < kMinDotUp) && !(t.x < kEpsUp) && !(s0.x > 0.f) && !(s1.x > 0.f) &&
+                  !(s2.x > 0.f);
+  const bool vb = !(fabsf(denom.y) < kMinDotUp) && !(t.y < kEpsUp) && !(s0.y > 0.f) && !(s1.y > 0.f) &&
+                  !(s2.y > 0.f);
+  const float tt = odd ? t.y : t.x, tp = odd ? t.x : t.y;
+  const bool hit = (odd ? vb : va) & !(tt >= __builtin_inff());
+  // tt >= kEpsUp > 0 and finite when it matters: +1 on the bits is nextup
+  const float bound = odd ? __uint_as_float(__float_as_uint(tt) + 1u) : tt;
+  const bool occ = (odd ? va : vb) & (tp < bound);
+  te = hit ? tt : __builtin_inff();
+  return hit & !occ;
+}
+
+#if IPT_SHADOW_PAIR1
+// allow_at(): the lane's potential-occluder mask, asked for only after the
+// target's pair is done (one register fewer across that test).
+template <class AllowAt>
+__device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *pairs_lds, const TriPair *__restrict__ pairs,
+                                                      const PairBox2 *__restrict__ boxes, const f2 *e3, int nT, V3 p,
+                                                      V3 d, int target, float &best_t, AllowAt allow_at) {
+  int nP = (nT + 1) >> 1;
+  asm volatile("" : "+s"(nP));
+  lds_f2c *e3l = (lds_f2c *)e3;
+  const int j = target >> 1, odd = target & 1;
+  float te = __builtin_inff();
+  bool live = false;
+#if IPT_SHADOW_PAIR1_SRC
+  // all lanes aim at one pair (one emitter quad: the common case): it comes
+  // in through scalar loads and is evaluated once, packed
+  const int js = __builtin_amdgcn_readfirstlane(j);
+  if (__builtin_amdgcn_ballot_w64(j != js) == 0) {
+    const TriPair T = pairs[js];
+    live = pair_target(T, pair_origin(T, p), odd, p, d, e3l[3 * js], e3l[3 * js + 1], e3l[3 * js + 2], te);
+  } else {
+    // mixed pairs in the wave: per lane, the two halves one after the other
+    // with hit_test's scalar arithmetic (fewer registers than a gathered pair)
+    float tp;
+    const bool vt = half_test(pairs_lds, pairs, 2 * j + odd, p, d, te);
+    const bool vp = half_test(pairs_lds, pairs, 2 * j + (odd ^ 1), p, d, tp);
+    const bool hit = vt & !(te >= __builtin_inff());
+    const float bound = odd ? __uint_as_float(__float_as_uint(te) + 1u) : te;
+    live = hit & !(vp & (tp < bound));
+    te = hit ? te : __builtin_inff();
+  }
+#else
+  {
+    const TriPair T = load_pair_lds(pairs_lds, j);
+    live = pair_target(T, pair_origin(T, p), odd, p, d, e3l[3 * j], e3l[3 * j + 1], e3l[3 * j + 2], te);
+  }
+#endif
+  const uint32_t rest = allow_at() & ~(1u << j);  // the target's own pair is done
+#ifdef IPT_BVH_STATS
+  atomicAdd(&g_bvh_stats[12], 1ull);                      // shadow lanes
+  if (!(te >= __builtin_inff())) atomicAdd(&g_bvh_stats[13], 1ull);  // ... whose target is accepted
+  atomicAdd(&g_bvh_stats[16], 1ull);                      // lane pair tests (the target's pair)
+  if (__lane_id() == __ffsll((unsigned long long)__builtin_amdgcn_ballot_w64(true)) - 1) {
+    atomicAdd(&g_bvh_stats[14], 1ull);                    // wave-level calls
+    atomicAdd(&g_bvh_stats[15], 1ull);                    // wave-level pair tests (the target's pair)
+  }
+#endif
+  // nothing left that could occlude any live lane: no slab setup, no box
+  // tests, no pair loop (every test skipped here had need = 0)
+  if (__builtin_amdgcn_ballot_w64(live && rest != 0u)) {
+#ifdef IPT_BVH_STATS
+    if (live) atomicAdd(&g_bvh_stats[17], (unsigned long long)nP);  // lane box tests
+#endif
+    // opaque per cast: the compiler would otherwise hoist the loop-invariant
+    // box loads out of the megakernel loop into SGPRs, which then spill
+    asm volatile("" : "+s"(boxes));
+    const uint32_t need = live ? pair_box_bits(boxes, nP, p, d, te, rest) : 0u;
+    // (the LDS base pinned only now: pinned ahead of the box tests it cost the
+    // unbounded adjoint 4 B of scratch per lane)
+    if (IPT_PIN_E3) asm volatile("" : "+v"(e3l));
+    live = occlusion_pass([&](int k) { return pairs[k]; }, [&](int k) { return k; }, e3l, nP, need, p, d, target, te,
+                          live);
+  }
+  best_t = te;
+  return live ? target : -1;
+}
+#else
 // The target's record comes from the workgroup's LDS copy of the TriIsect array.
+template <class AllowAt>
 __device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *isect_lds, const TriPair *__restrict__ pairs,
                                                       const PairBox2 *__restrict__ boxes, const f2 *e3, int nT, V3 p,
-                                                      V3 d, int target, float &best_t, uint32_t allow = 0xffffffffu) {
+                                                      V3 d, int target, float &best_t, AllowAt allow_at) {
+  const uint32_t allow = allow_at();
   float bt = __builtin_inff();
   int bi = -1;
   bool live;
@@ -747,6 +909,7 @@ __device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *isect_lds, 
   best_t = bt;
   return bi;
 }
+#endif  // IPT_SHADOW_PAIR1
 
 // Path ray of the small-scene loop with per-lane pair culling
 // (IPT_PATH_CULL): a lane tests only the pairs whose acceptance box its ray

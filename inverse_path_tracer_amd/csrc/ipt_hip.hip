@@ -1277,7 +1277,7 @@ static size_t bvh_lds(const GpuScene *s, TraceArgs &a, size_t base, bool stage =
 
 static size_t table_bytes(const TraceArgs &a) {
   return (a.kd_tables ? (size_t)6 * a.nT * sizeof(float) : 0) +
-         (a.small_pairs ? (size_t)kE3Floats * ((a.nT + 1) / 2) * sizeof(float) + 12 + (size_t)a.nT * sizeof(TriIsect) +
+         (a.small_pairs ? (size_t)kE3Floats * ((a.nT + 1) / 2) * sizeof(float) + 12 + (size_t)a.nT * kIsectLdsFloats * sizeof(float) +
                               (IPT_PATH_CULL ? (size_t)((a.nT + 1) / 2) * sizeof(TriPair) : 0) +
                               (IPT_SHADOW_PO && a.pomask ? (size_t)a.nT * a.nE * sizeof(uint32_t) : 0)
                         : 0);
@@ -2043,13 +2043,13 @@ __global__ __launch_bounds__(kBlock) void closest_hit_kernel(const TriIsect *__r
     for (int i = tid; i < kE3Floats * nP; i += kBlock) lds_e3[i] = small_table_entry(pairs, i);
     e3 = reinterpret_cast<const f2 *>(lds_e3);
   }
-  // the culled shadow cast's LDS copy of the TriIsect records (!BVH, small)
+  // the two-step shadow cast's LDS copy of the TriIsect records (!BVH, small, IPT_SHADOW_PAIR1=0)
   float *lds_is = lds_e3 + kE3Floats * nP;
   lds_is += (4 - (int)((lds_is - lds_e3) & 3)) & 3;
-  float *lds_pr = lds_is + 20 * nT;  // the culled path cast's TriPair copy (!BVH, small)
+  float *lds_pr = lds_is + kIsectLdsFloats * nT;  // the culled path cast's TriPair copy (!BVH, small)
   if (!BVH && small) {
     const float *g = reinterpret_cast<const float *>(isect);
-    for (int i = tid; i < 20 * nT; i += kBlock) lds_is[i] = g[i];
+    for (int i = tid; i < kIsectLdsFloats * nT; i += kBlock) lds_is[i] = g[i];
     if (IPT_PATH_CULL) {
       const float *gp = reinterpret_cast<const float *>(pairs);
       for (int i = tid; i < 36 * nP; i += kBlock) lds_pr[i] = gp[i];
@@ -2128,8 +2128,10 @@ __global__ __launch_bounds__(kBlock) void closest_hit_kernel(const TriIsect *__r
     coop_cast<true>(cv, qn && target >= 0, p, d, t, h);
   } else if (valid) {
     if (IPT_SHADOW_CULL && small && target >= 0) {  // the megakernel's shadow cast of small scenes
-      const uint32_t allow = probe_allow(IPT_SHADOW_PO ? a.pomask : nullptr, emit_tri, a.nE, nT, src, target);
-      h = shadow_hit_pairs_small((const lds_f32 *)lds_is, pairs, a.pboxes, e3, nT, p, d, target, t, allow);
+      h = shadow_hit_pairs_small((const lds_f32 *)(IPT_SHADOW_PAIR1 ? lds_pr : lds_is), pairs, a.pboxes, e3, nT, p, d,
+                                 target, t, [&]() {
+                                   return probe_allow(IPT_SHADOW_PO ? a.pomask : nullptr, emit_tri, a.nE, nT, src, target);
+                                 });
     } else if (IPT_PATH_CULL && small && targets && target < 0) {  // ... and its path cast
       h = closest_hit_pairs_culled((const lds_f32 *)lds_pr, a.pboxes, nT, p, d, t);
     } else {  // the full closest hit (brute-force pair loop)
@@ -2172,7 +2174,7 @@ int gpu_closest_hit(GpuScene *s, int64_t n, const float *org_dev, const float *d
     hipLaunchKernelGGL(closest_hit_kernel<true>, dim3(blocks), dim3(kBlock), lds, (hipStream_t)stream, s->isect,
                        s->pairs, a, small, n, org_dev, dir_dev, targets_dev, sources_dev, s->emit_tri, t_dev, idx_dev);
   } else {
-    const size_t lds = base + (small ? 12 + (size_t)s->host.nT * sizeof(TriIsect) +
+    const size_t lds = base + (small ? 12 + (size_t)s->host.nT * kIsectLdsFloats * sizeof(float) +
                                            (IPT_PATH_CULL ? (size_t)((s->host.nT + 1) / 2) * sizeof(TriPair) : 0)
                                      : 0);
     hipLaunchKernelGGL(closest_hit_kernel<false>, dim3(blocks), dim3(kBlock), lds, (hipStream_t)stream, s->isect,

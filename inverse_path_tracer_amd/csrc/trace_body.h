@@ -73,17 +73,17 @@
     for (int i = tid; i < kE3Floats * nP; i += nthr) lds_e3[i] = small_table_entry(pairs, i);
     e3 = reinterpret_cast<const f2 *>(lds_e3);
   }
-  // small scenes: a copy of the TriIsect records (16-B aligned), read by the
-  // culled shadow cast's per-lane target test from LDS instead of L2
+  // small scenes, two-step shadow cast only (IPT_SHADOW_PAIR1=0): a copy of
+  // the TriIsect records (16-B aligned), read by its per-lane target test
   float *lds_is = lds_e3 + (a.small_pairs ? kE3Floats * nP : 0);
   lds_is += (4 - (int)((lds_is - reinterpret_cast<float *>(lds)) & 3)) & 3;
-  if (a.small_pairs) {
+  if (kIsectLdsFloats != 0 && a.small_pairs) {
     const float *g = reinterpret_cast<const float *>(isect);
-    for (int i = tid; i < 20 * nT; i += nthr) lds_is[i] = g[i];
+    for (int i = tid; i < kIsectLdsFloats * nT; i += nthr) lds_is[i] = g[i];
   }
   // small scenes, culled path cast (IPT_PATH_CULL): a copy of the TriPair
-  // records (16-B aligned after the TriIsect copy), gathered per lane
-  float *lds_pr = lds_is + (a.small_pairs ? 20 * nT : 0);
+  // records (16-B aligned), gathered per lane
+  float *lds_pr = lds_is + (a.small_pairs ? kIsectLdsFloats * nT : 0);
   if (a.small_pairs && IPT_PATH_CULL) {
     const float *g = reinterpret_cast<const float *>(pairs);
     for (int i = tid; i < 36 * nP; i += nthr) lds_pr[i] = g[i];
@@ -312,7 +312,12 @@
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the slots' sample writes before the sums
     __builtin_amdgcn_wave_barrier();
     const int m = __popc(mask);
-    const int kq = (lane * 43) >> 7, ch = lane - 3 * kq;  // lane / 3 for lane < 64
+    const int kq = (lane * 43) >> 7;  // lane / 3 for lane < 64
+    int ch = lane - 3 * kq;
+    // opaque per sum: left alone, the compiler forms the lane's output
+    // pointer (out_samples + ch) once before the trace loop and holds the two
+    // VGPRs through it for this one store per pixel
+    asm volatile("" : "+v"(ch));
     int slot = 0;
     uint32_t mm = mask;
     for (int i = 0; i < m; ++i) {  // wave-uniform: this lane's slot = the kq-th set bit
@@ -629,8 +634,8 @@
         SUBPHASE_END(9)
       } else if (shadow) {
         if (IPT_SHADOW_CULL && e3)
-          hs = shadow_hit_pairs_small((const lds_f32 *)lds_is, pairs, a.pboxes, e3, nT, p, sd, et, ts,
-                                      po ? ((const lds_u32c *)lds_po)[tri * nE + emitter] : 0xffffffffu);
+          hs = shadow_hit_pairs_small((const lds_f32 *)(IPT_SHADOW_PAIR1 ? lds_pr : lds_is), pairs, a.pboxes, e3, nT, p, sd, et, ts,
+                                      [&]() { return po ? ((const lds_u32c *)lds_po)[tri * nE + emitter] : 0xffffffffu; });
         else
           hs = cast_bf(pairs, e3, nT, p, sd, ts);
       }
