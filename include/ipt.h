@@ -241,6 +241,25 @@ int ipt_render_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, 
 int ipt_adjoint_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
                         const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
 int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj /*H*W*3*/, double *grad /*3*nT*3*/);
+/* The scene batch of the two, with ipt_render_batch_dev's conventions:
+ * n_scenes material sets over one geometry in one launch, set b with seed
+ * p->seed + b*seed_stride.  kd_dev / ks_dev / ke_dev: n_scenes*nT*3 floats
+ * [set][tri][c], each nullable (NULL = the scene's own values in every set).
+ * hdr_dev: n_scenes*rows*W*3; adj_dev: n_scenes full frames indexed by global
+ * pixel; p's row band and row_step are honoured.  grad_dev: n_scenes*3*nT*3
+ * doubles, [set][Kd | Ks | Ke][tri][c], ACCUMULATED.  Set b equals
+ * ipt_render_mat_dev / ipt_adjoint_mat_dev of its arrays and seed (images bit
+ * for bit, gradients to fp64 summation order); n_scenes == 1 is the
+ * single-set call.  Refused with an error before anything is enqueued:
+ * n_scenes < 1, a host-only scene, max_bounces < 0 or > 62, more than 65535
+ * triangles, an LDS footprint (one set's: a workgroup holds one set) over
+ * 160 KiB.  (Additive symbols: ipt_abi_version stays 5.) */
+int ipt_render_mat_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride,
+                             const float *kd_dev, const float *ks_dev, const float *ke_dev, float *hdr_dev,
+                             void *stream);
+int ipt_adjoint_mat_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride,
+                              const float *kd_dev, const float *ks_dev, const float *ke_dev, const float *adj_dev,
+                              double *grad_dev, void *stream);
 
 /* PNG helpers (RGB8). ipt_png_read with rgb == NULL only reports the size. */
 int ipt_png_write(const char *path, int width, int height, const uint8_t *rgb);

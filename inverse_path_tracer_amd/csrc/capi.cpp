@@ -507,6 +507,34 @@ int ipt_adjoint_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint
   return gpu_status(ipt::gpu_adjoint(s, r, kd_dev, adj_dev, grad_dev, stream));
 }
 
+int ipt_render_mat_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride,
+                             const float *kd_dev, const float *ks_dev, const float *ke_dev, float *hdr_dev,
+                             void *stream) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !hdr_dev || n_scenes < 1) {
+    if (s) fail("ipt_render_mat_batch_dev: bad arguments (scene, params and hdr_dev are required, n_scenes >= 1)");
+    return -1;
+  }
+  ipt::RenderParams r = to_params(p);
+  r.nscenes = n_scenes;
+  r.seed_stride = seed_stride;
+  return gpu_status(ipt::gpu_render_mat_batch(s, r, kd_dev, ks_dev, ke_dev, hdr_dev, stream));
+}
+
+int ipt_adjoint_mat_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride,
+                              const float *kd_dev, const float *ks_dev, const float *ke_dev, const float *adj_dev,
+                              double *grad_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !adj_dev || !grad_dev || n_scenes < 1) {
+    if (s) fail("ipt_adjoint_mat_batch_dev: bad arguments (scene, params, adj_dev and grad_dev are required, n_scenes >= 1)");
+    return -1;
+  }
+  ipt::RenderParams r = to_params(p);
+  r.nscenes = n_scenes;
+  r.seed_stride = seed_stride;
+  return gpu_status(ipt::gpu_adjoint_mat_batch(s, r, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream));
+}
+
 int ipt_graph_dev(void *scene, const ipt_params_t *p, const uint8_t *target_dev, double *acc_dev, void *stream) {
   GpuScene *s = as_scene(scene);
   if (!s || !p || !target_dev || !acc_dev) return -1;

@@ -51,6 +51,14 @@ int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, cons
 int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
                     const float *adj_dev, double *grad_dev, void *stream);
 int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad);
+// The scene batch of the two (p.nscenes sets, p.seed_stride): kd / ks / ke are n_scenes*nT*3
+// (nullptr = the scene's own values in every set); hdr_dev n_scenes images, grad_dev
+// n_scenes x 3 x nT x 3 doubles [set][Kd | Ks | Ke], accumulated.  Set b is the single-set
+// call with its arrays and seed + b * seed_stride.  Bounded estimator only.
+int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                         const float *ke_dev, float *hdr_dev, void *stream);
+int gpu_adjoint_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                          const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
 
 // Host-memory conveniences (allocate, copy, run, copy back, synchronize).
 int gpu_render_samples_host(GpuScene *s, const RenderParams &p, float *samples);

@@ -323,6 +323,11 @@ struct TraceArgs {
   // chunk_small (units: work items, or pixels in MODE_FWDM), so a launch ends
   // on small chunks and its waves run dry close together (chunk_range)
   uint32_t chunk_small, chunk_big_n;
+  // scene batch with per-set TriMat tables (the material overrides' batch):
+  // set b reads mat + b * mat_stride records; 0 = one table for every set.
+  // (Here, in what was padding before chunk_ctr: the kernarg layout of every
+  // other field is the one the single-set instances were tuned with.)
+  uint32_t mat_stride;
   // the launch's grab counters (one word per material set or XCD region).
   // Each wave grabs until one grab fails, so a word ends a launch at
   // `grabs` (launch_grabs: a function of the launch's shape, like the chunk
@@ -355,6 +360,7 @@ struct TraceArgs {
   uint8_t *ldr;
 };
 static_assert(alignof(TraceArgs) == 8, "TraceArgs sits right after the ten 8-B scene pointers in the kernarg segment");
+static_assert(offsetof(TraceArgs, chunk_ctr) == offsetof(TraceArgs, mat_stride) + sizeof(uint32_t), "mat_stride fills the padding");
 
 __device__ __forceinline__ uint32_t udiv32(uint32_t n, uint64_t m, uint32_t d) {
   return d == 1u ? n : (uint32_t)__umul64hi(m, (uint64_t)n);
@@ -746,6 +752,27 @@ __global__ IPT_TRACE_BOUNDS void trace_kernel(
     float *__restrict__ out_samples, const float *__restrict__ adj, double *__restrict__ grad,
     const uint8_t *__restrict__ target, double *__restrict__ edges) {
   constexpr bool MATG = false;
+  constexpr bool MATB = false;
+  const int *const tri_emit = nullptr;
+#include "trace_body.h"
+}
+
+// The forward of a scene batch whose sets have their own TriMat tables (the
+// material overrides' batch): trace_kernel's forward instances
+// with mat offset per set (MATB).  Instances of their own, because that one
+// offset inside trace_kernel's body moved the register allocation and the
+// schedule of the tuned single-set forwards (the C2 headline +0.10%, three
+// sessions alike); so trace_kernel's 21 instances stay what they were.
+template <int MODE, bool SPEC, bool BVH>
+__global__ IPT_TRACE_BOUNDS void trace_fwd_mat_kernel(
+    const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+    const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat, const float *__restrict__ kd,
+    const int *__restrict__ emit_tri, const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+    float *__restrict__ out_samples, const float *__restrict__ adj, double *__restrict__ grad,
+    const uint8_t *__restrict__ target, double *__restrict__ edges) {
+  static_assert(is_fwd<MODE>(), "forward instances only");
+  constexpr bool MATG = false;
+  constexpr bool MATB = true;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -765,29 +792,40 @@ trace_mat_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const Tr
                  const int *__restrict__ tri_emit) {
   constexpr int MODE = MODE_ADJ;
   constexpr bool MATG = true;
+  constexpr bool MATB = false;
 #include "trace_body.h"
 }
 
-// Per-launch TriMat table of the material overrides (stream scratch): the
+// Per-launch TriMat tables of the material overrides (stream scratch): the
 // scene's entries with ks / ke replaced from nT*3 device arrays (nullptr: the
 // scene's own); flags and shininess are kept, and rows outside the lobe /
-// emitter masks fixed at load are forced to 0.
+// emitter masks fixed at load are forced to 0.  Scene batch: blockIdx.y =
+// material set, ks / ke [set][tri][c], one table of nT records per set.
 __global__ __launch_bounds__(kBlock) void pack_mat_kernel(const TriMat *__restrict__ src, const float *__restrict__ ks,
                                                           const float *__restrict__ ke,
                                                           const int *__restrict__ tri_emit, int nT,
                                                           TriMat *__restrict__ out) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= nT) return;
+  const size_t row = (size_t)blockIdx.y * (size_t)nT + (size_t)i;
   TriMat m = src[i];
   if (ks) {
     const bool lobe = (m.flags & MAT_HAS_KS) != 0;
-    for (int c = 0; c < 3; ++c) m.ks[c] = lobe ? ks[3 * i + c] : 0.f;
+    for (int c = 0; c < 3; ++c) m.ks[c] = lobe ? ks[3 * row + c] : 0.f;
   }
   if (ke) {
     const bool em = tri_emit[i] >= 0;
-    for (int c = 0; c < 3; ++c) m.ke[c] = em ? ke[3 * i + c] : 0.f;
+    for (int c = 0; c < 3; ++c) m.ke[c] = em ? ke[3 * row + c] : 0.f;
   }
-  out[i] = m;
+  out[row] = m;
+}
+
+// out[i] = src[i % n], i < total: the scene's own kd for every set of a batch
+// whose caller gave none (the kernels read kd + set * 3 nT).
+__global__ __launch_bounds__(kBlock) void replicate_kernel(const float *__restrict__ src, int n, size_t total,
+                                                           float *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < total) out[i] = src[i % (size_t)n];
 }
 
 // toneMap over a sample-major buffer [s][pixel][3]: same per-pixel
@@ -913,13 +951,14 @@ struct GpuScene {
   int adju_nl = 0;       // ... made for this LDS base
   int *grad_map = nullptr, *slot_tri = nullptr;  // ADJ hot-set LDS slots (large scenes)
   int *tri_emit = nullptr;  // triangle -> emitter index or -1 (material overrides and adjoint)
-  // slots 0..23: trace_kernel<mode, spec, bvh>; 24..27: trace_mat_kernel<spec, bvh> (inst_slot)
-  int grid[28] = {0};       // resident workgroups per instance (0 = not queried)
-  size_t grid_lds[28] = {0};
-  size_t pick_base[28] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
-  size_t pick_tail[28] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
-  int pick_opt[28] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  // slots 0..23: trace_kernel<mode, spec, bvh>; 24..27: trace_mat_kernel<spec, bvh>;
+  // 28..35: trace_fwd_mat_kernel<FWD | FWDM, spec, bvh> (inst_slot)
+  int grid[36] = {0};       // resident workgroups per instance (0 = not queried)
+  size_t grid_lds[36] = {0};
+  size_t pick_base[36] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
+  size_t pick_tail[36] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
+  int pick_opt[36] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
+                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   // dynamic-chunk counters per stream (stream_counters): `words` grab words,
   // zeroed once; every launch leaves them zero (TraceArgs::chunk_ctr)
   struct Counters {
@@ -1125,19 +1164,28 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 #ifndef IPT_DEBUG_GRID
 #define IPT_DEBUG_GRID 0
 #endif
-// An instance's slot in GpuScene's per-instance caches: trace_kernel<MODE,
-// SPEC, BVH>, or (MATG, MODE_ADJ only) the material adjoint trace_mat_kernel<SPEC, BVH>.
-template <int MODE, bool SPEC, bool BVH, bool MATG>
+// The kernel a launch runs: trace_kernel<MODE, SPEC, BVH>, or (MODE_ADJ only)
+// the material adjoint trace_mat_kernel<SPEC, BVH>, or (the forwards only) the
+// batch forward with per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
+enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2 };
+// An instance's slot in GpuScene's per-instance caches.
+template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr int inst_slot() {
-  return MATG ? 24 + (SPEC ? 2 : 0) + (BVH ? 1 : 0) : MODE * 4 + (SPEC ? 2 : 0) + (BVH ? 1 : 0);
+  return (KIND == KIND_MATG   ? 24
+          : KIND == KIND_FWDB ? 28 + (MODE == MODE_FWDM ? 4 : 0)
+                              : MODE * 4) +
+         (SPEC ? 2 : 0) + (BVH ? 1 : 0);
 }
-template <int MODE, bool SPEC, bool BVH, bool MATG = false>
+template <int MODE, bool SPEC, bool BVH, int KIND = KIND_TRACE>
 static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
-  const int slot = inst_slot<MODE, SPEC, BVH, MATG>();
+  const int slot = inst_slot<MODE, SPEC, BVH, KIND>();
   if (s->grid[slot] == 0 || s->grid_lds[slot] != lds_bytes) {
     int per_cu = 0, cus = 0;
-    if constexpr (MATG) {
+    if constexpr (KIND == KIND_MATG) {
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_mat_kernel<SPEC, BVH>, kBlock, lds_bytes));
+    } else if constexpr (KIND == KIND_FWDB) {
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, BVH>, kBlock,
+                                                           lds_bytes));
     } else {
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<MODE, SPEC, BVH>, kBlock,
                                                            lds_bytes));
@@ -1151,7 +1199,10 @@ static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
     s->grid_lds[slot] = lds_bytes;
     if (IPT_DEBUG_GRID)  // (make variant DEFS=-DIPT_DEBUG_GRID=1)
       std::fprintf(stderr, "[ipt] %s<%d,%d,%d>: %zu B LDS/block, %d blocks/CU x %d CUs\n",
-                   MATG ? "trace_mat_kernel" : "trace_kernel", MODE, (int)SPEC, (int)BVH, lds_bytes, per_cu, cus);
+                   KIND == KIND_MATG   ? "trace_mat_kernel"
+                   : KIND == KIND_FWDB ? "trace_fwd_mat_kernel"
+                                       : "trace_kernel",
+                   MODE, (int)SPEC, (int)BVH, lds_bytes, per_cu, cus);
   }
   *grid = s->grid[slot];
   return 0;
@@ -1229,6 +1280,7 @@ static TraceArgs make_args(const GpuScene *s, const RenderParams &p) {
   a.big_pomask = nullptr;  // set with the other BVH fields (bvh_lds)
   a.nscenes = p.nscenes > 1 ? p.nscenes : 1;
   a.bps = 1;
+  a.mat_stride = 0;  // launch(): nT for a batch with its own TriMat tables
   a.seed_stride = p.seed_stride;
   a.out_stride = a.n_samples * 3;
   a.adj_stride = (uint64_t)p.width * p.height * 3;
@@ -1387,7 +1439,7 @@ static uint32_t launch_grabs(bool guided, uint64_t units, uint64_t c, uint64_t s
 
 // mat_dev: the launch's TriMat table (nullptr: the scene's own; the material
 // overrides pass the table pack_mat_kernel wrote).
-template <int MODE, bool SPEC, bool BVH, bool MATG = false>
+template <int MODE, bool SPEC, bool BVH, int KIND = KIND_TRACE>
 static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float *kd_dev, float *out, const float *adj,
                        double *grad, const uint8_t *target, double *edges, hipStream_t st,
                        const TriMat *mat_dev = nullptr) {
@@ -1396,7 +1448,7 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float 
     gpu_set_error("LDS footprint of the launch exceeds 160 KiB");
     return -1;
   }
-  if (resident_grid<MODE, SPEC, BVH, MATG>(s, lds, &grid)) return -1;
+  if (resident_grid<MODE, SPEC, BVH, KIND>(s, lds, &grid)) return -1;
   if (a.n_samples == 0) return 0;
   TraceArgs b = a;
   if (a.nscenes > 1) {  // scene batch: an equal share of the resident blocks per material set
@@ -1463,10 +1515,14 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float 
     return -1;
   }
   const TriMat *mat = mat_dev ? mat_dev : s->mat;
-  if constexpr (MATG)
+  if constexpr (KIND == KIND_MATG)
     hipLaunchKernelGGL((trace_mat_kernel<SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs, s->geom,
                        mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad, target,
                        edges, s->tri_emit);
+  else if constexpr (KIND == KIND_FWDB)
+    hipLaunchKernelGGL((trace_fwd_mat_kernel<MODE, SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect,
+                       s->pairs, s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out,
+                       adj, grad, target, edges);
   else
     hipLaunchKernelGGL((trace_kernel<MODE, SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs,
                        s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad,
@@ -1492,9 +1548,9 @@ __global__ __launch_bounds__(kBlock) void kdpi_kernel(const float *__restrict__ 
 // resident workgroups per CU.  North-star adjoint: the tree stage + records +
 // bins sit just under 3 workgroups/CU, and the pair copy would tip it to 2
 // (6.6 -> 7.9 ms).  Cached per scene and instance for the base LDS bytes.
-template <int MODE, bool SPEC, bool MATG = false>
+template <int MODE, bool SPEC, int KIND = KIND_TRACE>
 static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) {
-  const int slot = inst_slot<MODE, SPEC, false, MATG>();
+  const int slot = inst_slot<MODE, SPEC, false, KIND>();
   const bool opt[4][2] = {{true, true}, {true, false}, {false, true}, {false, false}};
   const size_t base = *lds;
   if (s->pick_opt[slot] < 0 || s->pick_base[slot] != base || s->pick_tail[slot] != tail) {
@@ -1504,8 +1560,10 @@ static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) 
       const size_t l = bvh_lds_offset(bvh_lds(s, b, base, opt[k][0], opt[k][1], is_fwd<MODE>())) + tail;
       if (l > 160 * 1024) continue;
       int per_cu = 0;
-      if constexpr (MATG) {
+      if constexpr (KIND == KIND_MATG) {
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_mat_kernel<SPEC, true>, kBlock, l));
+      } else if constexpr (KIND == KIND_FWDB) {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, true>, kBlock, l));
       } else {
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<MODE, SPEC, true>, kBlock, l));
       }
@@ -1529,10 +1587,17 @@ static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) 
 
 // tail: bytes per workgroup placed after everything else (16-B aligned; the
 // fused pixel mean's sample slots, TraceArgs::mean_off).
-template <int MODE, bool MATG = false>
+template <int MODE, int KIND = KIND_TRACE>
 static int launch(GpuScene *s, TraceArgs a, size_t lds, const float *kd_dev, float *out, const float *adj,
                   double *grad, const uint8_t *target, double *edges, hipStream_t st, size_t tail = 0,
                   const TriMat *mat_dev = nullptr) {
+  // a batch's per-launch table holds one TriMat table per set (pack_materials);
+  // its forward runs the instances that offset mat per set
+  a.mat_stride = (mat_dev && a.nscenes > 1) ? (uint32_t)a.nT : 0u;
+  if constexpr (is_fwd<MODE>() && KIND == KIND_TRACE) {
+    if (a.mat_stride)
+      return launch<MODE, KIND_FWDB>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, tail, mat_dev);
+  }
   StreamScratch kdpi;
   if (MODE != MODE_GRAPH && !a.kd_tables && a.n_samples > 0) {
     const int n = 3 * s->host.nT * a.nscenes;
@@ -1553,18 +1618,18 @@ static int launch(GpuScene *s, TraceArgs a, size_t lds, const float *kd_dev, flo
     return launch_inst<MODE, false, false>(s, a, lds, kd_dev, out, adj, grad, target, edges, st);
   } else if (use_bvh(s)) {
     if (s->has_ks) {
-      if (launch_bvh_pick<MODE, true, MATG>(s, a, &lds, tail)) return -1;
+      if (launch_bvh_pick<MODE, true, KIND>(s, a, &lds, tail)) return -1;
       add_tail();
-      return launch_inst<MODE, true, true, MATG>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+      return launch_inst<MODE, true, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
     }
-    if (launch_bvh_pick<MODE, false, MATG>(s, a, &lds, tail)) return -1;
+    if (launch_bvh_pick<MODE, false, KIND>(s, a, &lds, tail)) return -1;
     add_tail();
-    return launch_inst<MODE, false, true, MATG>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+    return launch_inst<MODE, false, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
   } else {
     add_tail();
     if (s->has_ks)
-      return launch_inst<MODE, true, false, MATG>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
-    return launch_inst<MODE, false, false, MATG>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+      return launch_inst<MODE, true, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+    return launch_inst<MODE, false, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
   }
 }
 
@@ -1723,19 +1788,54 @@ int gpu_set_material_params(GpuScene *s, const float *kd, const float *ks, const
   return 0;
 }
 
-// The launch's TriMat table for ks / ke overrides (device arrays, nT*3 each):
-// *mat stays nullptr (the scene's own table) when both are null.
-static int pack_materials(GpuScene *s, const float *ks_dev, const float *ke_dev, hipStream_t st, StreamScratch &buf,
-                          const TriMat **mat) {
+// The launch's TriMat tables for ks / ke overrides (device arrays, sets*nT*3
+// each): one table per material set, written by one launch; *mat stays
+// nullptr (the scene's own table, for every set) when both are null.
+static int pack_materials(GpuScene *s, const float *ks_dev, const float *ke_dev, int sets, hipStream_t st,
+                          StreamScratch &buf, const TriMat **mat) {
   *mat = nullptr;
   if (!ks_dev && !ke_dev) return 0;
   const int nT = s->host.nT;
-  if (buf.alloc((size_t)nT * sizeof(TriMat), st)) return -1;
-  hipLaunchKernelGGL(pack_mat_kernel, dim3((nT + kBlock - 1) / kBlock), dim3(kBlock), 0, st, s->mat, ks_dev, ke_dev,
-                     s->tri_emit, nT, (TriMat *)buf.p);
+  if (buf.alloc((size_t)sets * nT * sizeof(TriMat), st)) return -1;
+  hipLaunchKernelGGL(pack_mat_kernel, dim3((nT + kBlock - 1) / kBlock, sets), dim3(kBlock), 0, st, s->mat, ks_dev,
+                     ke_dev, s->tri_emit, nT, (TriMat *)buf.p);
   HIP_TRY(hipGetLastError());
   *mat = (const TriMat *)buf.p;
   return 0;
+}
+
+// A batch's kd: the caller's sets*nT*3 array, or the scene's own kd repeated
+// for every set (stream scratch, on the launch's stream).
+static int batch_kd(GpuScene *s, const float **kd_dev, int sets, hipStream_t st, StreamScratch &buf) {
+  if (*kd_dev || sets <= 1) return 0;
+  const int n = 3 * s->host.nT;
+  const size_t total = (size_t)sets * n;
+  if (buf.alloc(total * sizeof(float), st)) return -1;
+  hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s->kd, n,
+                     total, (float *)buf.p);
+  HIP_TRY(hipGetLastError());
+  *kd_dev = (const float *)buf.p;
+  return 0;
+}
+
+// The batched material launches' limit on the number of sets, checked before
+// anything is enqueued.
+static int check_sets(int n_scenes) {
+  if (n_scenes > 65535) {  // pack_mat_kernel's blockIdx.y
+    gpu_set_error("material overrides: at most 65535 material sets per launch");
+    return -1;
+  }
+  return 0;
+}
+
+static int render_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                           const float *ke_dev, float *hdr_dev, uint8_t *ldr_dev, void *stream) {
+  const int sets = p.nscenes > 1 ? p.nscenes : 1;
+  StreamScratch tab, kdrep;  // freed behind the launch, in stream order
+  const TriMat *mat = nullptr;
+  if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
+  if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
+  return render_impl(s, p, kd_dev, hdr_dev, ldr_dev, stream, mat);
 }
 
 int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
@@ -1745,23 +1845,54 @@ int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, cons
     gpu_set_error("material overrides do not support the scene batch (n_scenes > 1)");
     return -1;
   }
-  StreamScratch tab;  // freed behind the launch, in stream order
-  const TriMat *mat = nullptr;
-  if (pack_materials(s, ks_dev, ke_dev, (hipStream_t)stream, tab, &mat)) return -1;
-  return render_impl(s, p, kd_dev, hdr_dev, ldr_dev, stream, mat);
+  return render_mat_impl(s, p, kd_dev, ks_dev, ke_dev, hdr_dev, ldr_dev, stream);
+}
+
+// The scene batch of gpu_render_mat: kd / ks / ke are n_scenes*nT*3 (nullptr:
+// the scene's own values in every set), hdr_dev n_scenes images; set b is
+// gpu_render_mat with its arrays and seed + b * seed_stride, bit for bit.
+int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                         const float *ke_dev, float *hdr_dev, void *stream) {
+  if (check_params(s, p) || check_sets(p.nscenes)) return -1;
+  // the forward's own bounce limit is the adjoint's: one contract for the pair
+  if (p.max_bounces < 0 || p.max_bounces > kMaxAdjBounces) {
+    gpu_set_error("material batch: give max_bounces in 0..62 (the unbounded estimator is not supported)");
+    return -1;
+  }
+  if (s->host.nT > kMaxAdjTris) {
+    gpu_set_error("material batch supports at most 65535 triangles");
+    return -1;
+  }
+  return render_mat_impl(s, p, kd_dev, ks_dev, ke_dev, hdr_dev, nullptr, stream);
 }
 
 // dL/dKd, dL/dKs, dL/dKe in one launch of trace_mat_kernel (the bounded
 // adjoint only); grad_dev: 3 x nT x 3 doubles [Kd | Ks | Ke], accumulated.
+static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                            const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
 int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
                     const float *adj_dev, double *grad_dev, void *stream) {
   if (check_params(s, p)) return -1;
-  if (p.max_bounces < 0) {
-    gpu_set_error("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; give max_bounces in 0..62");
+  if (p.nscenes > 1 && p.max_bounces >= 0) {  // (the unbounded refusal comes first, as it always did)
+    gpu_set_error("material adjoint: the scene batch (n_scenes > 1) is not supported");
     return -1;
   }
-  if (p.nscenes > 1) {
-    gpu_set_error("material adjoint: the scene batch (n_scenes > 1) is not supported");
+  return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream);
+}
+
+// The scene batch of gpu_adjoint_mat: grad_dev is n_scenes x 3 x nT x 3
+// doubles [set][Kd | Ks | Ke][tri][c], accumulated; a workgroup holds one
+// set's bins and tables, so the LDS limit is the single-set one.
+int gpu_adjoint_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                          const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+  if (check_params(s, p) || check_sets(p.nscenes)) return -1;
+  return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream);
+}
+
+static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                            const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+  if (p.max_bounces < 0) {
+    gpu_set_error("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; give max_bounces in 0..62");
     return -1;
   }
   if (p.max_bounces > kMaxAdjBounces) {
@@ -1789,10 +1920,12 @@ int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, con
     gpu_set_error("material adjoint: LDS footprint (Kd/Ks/Ke bins + tables + vertex records) exceeds 160 KiB; lower max_bounces");
     return -1;
   }
-  StreamScratch tab;
+  const int sets = p.nscenes > 1 ? p.nscenes : 1;
+  StreamScratch tab, kdrep;
   const TriMat *mat = nullptr;
-  if (pack_materials(s, ks_dev, ke_dev, (hipStream_t)stream, tab, &mat)) return -1;
-  return launch<MODE_ADJ, true>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream, 0,
+  if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
+  if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
+  return launch<MODE_ADJ, KIND_MATG>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream, 0,
                                 mat);
 }
 

@@ -5,7 +5,8 @@
 // register allocation and scratch of the BVH instances of trace_kernel.
 // The including kernel provides, as template parameters or constexpr locals,
 // MODE, SPEC, BVH and MATG (the material adjoint: the bounded adjoint whose
-// sweep also emits dL/dKs and dL/dKe), the parameters of
+// sweep also emits dL/dKs and dL/dKe) and MATB (a forward whose
+// scene batch has one TriMat table per set), the parameters of
 // TraceKernArgs under their names, and tri_emit (MATG: triangle -> emitter
 // index or -1; nullptr otherwise).
   extern __shared__ double lds[];
@@ -17,8 +18,12 @@
   const uint64_t seed = a.seed + (uint64_t)set * a.seed_stride;
   if (a.nscenes > 1) {
     kd += (size_t)set * 3 * a.nT;
+    // per-set TriMat tables (0: one table for every set): the material
+    // adjoint, and the forward instances of the material overrides' batch
+    if (MATG || MATB) mat += (size_t)set * a.mat_stride;
     if (is_fwd<MODE>()) out_samples += (size_t)set * a.out_stride;
-    // (adj, grad: karg() at their uses, offset there)
+    // (adj, grad: karg() at their uses, offset there; a set's gradient is
+    // 3 nT doubles, or with MATG its [Kd | Ks | Ke] slice of 9 nT)
   }
   const float *kdpi_g = a.kdpi_g ? a.kdpi_g + (size_t)set * 3 * a.nT : nullptr;
   constexpr int nthr = kBlock;
@@ -1100,7 +1105,7 @@
             }
             const int sl = a.grad_map ? a.grad_map[tk] : tk;
             const double v[3] = {(double)(ax * gk.x), (double)(ay * gk.y), (double)(az * gk.z)};
-            double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (a.nscenes > 1 ? (size_t)set * 3 * a.nT : 0);
+            double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0);
             bins_add(sl >= 0, grad, sl >= 0 ? (size_t)sl * 3 : (size_t)tk * 3, 3, v);
             if (MATG) {  // dL/dKs[tk], dL/dKe[et_k], dL/dKe[tri_0] (global layout [Kd | Ks | Ke], nT*3 each)
               const size_t gs3 = (size_t)a.grad_slots * 3;
@@ -1187,7 +1192,7 @@
   if (!is_fwd<MODE>()) {
     __syncthreads();
     if (n_acc > 0) {
-      double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (a.nscenes > 1 ? (size_t)set * 3 * a.nT : 0)
+      double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0)
                                     : edges;
       const int nb5 = (nT + 1) * nT * kEdgeL;
       for (int i = tid; i < n_acc; i += nthr) {

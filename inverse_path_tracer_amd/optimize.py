@@ -27,6 +27,13 @@ the ground-truth Kd with many more samples).
   by all scenes -- their gradient is summed across scenes and ranks with a
   single RCCL all-reduce per step.
 
+* Specular and emission: ``MaterialOptimizer(learn=("ks", "ke"))`` (any subset
+  of kd, ks, ke) optimises those blocks through the batched material adjoint
+  (torch_ops.render_materials_batch): still one forward and one
+  adjoint launch per batch and step, over scenes that share geometry, emitter
+  list, lobe flags and exponents and differ only in the values of Kd, Ks, Ke.
+  The default, ``learn=("kd",)``, is the Kd-only path above, unchanged.
+
     python -m inverse_path_tracer_amd.optimize --scenes assets/scenes --n 13 --steps 200
 """
 from __future__ import annotations
@@ -35,7 +42,7 @@ import argparse
 import os
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -47,6 +54,9 @@ from .scene import Scene
 # ipt_scene_export_triangles columns holding the diffuse Kd (everything else
 # is geometry / other material fields that must agree for a batch)
 _KD_COLS = slice(25, 28)
+# ... and Kd, Ks, Ke together (28:31 Ks, 31:34 Ke): the values a material batch may differ in
+_MAT_COLS = slice(25, 34)
+_BLOCKS = ("kd", "ks", "ke")
 
 
 @dataclass
@@ -58,6 +68,12 @@ class SceneTask:
     kd: torch.Tensor              # parameters (nT, 3)
     history: List[float] = field(default_factory=list)
     index: int = 0                # global scene index (keys the task's sample streams)
+    # specular and emitted colour (nT, 3) and their ground truths: only for MaterialOptimizer(learn=...)
+    # with "ks" / "ke"; None = the geometry handle's own values
+    ks: Optional[torch.Tensor] = None
+    ke: Optional[torch.Tensor] = None
+    truth_ks: Optional[torch.Tensor] = None
+    truth_ke: Optional[torch.Tensor] = None
 
 
 def _scene_files(root: str, n: int) -> List[str]:
@@ -86,36 +102,70 @@ def _runs(idx: List[int], tasks: List[SceneTask], limit: int):
     return runs
 
 
-def _geometry_key(sc: Scene) -> bytes:
+def _geometry_key(sc: Scene, materials: bool = False) -> bytes:
+    """What the scenes of one batch must share.  Kd-only batches: everything
+    but Kd.  Material batches: everything but the VALUES of Kd, Ks, Ke -- the
+    emitter list (column 56), the exponent (34) and the lobe flags are
+    structure, fixed when the geometry handle is loaded."""
     t = sc.triangles()
-    return np.concatenate([t[:, :_KD_COLS.start], t[:, _KD_COLS.stop:]], axis=1).tobytes()
+    cols = _MAT_COLS if materials else _KD_COLS
+    parts = [t[:, :cols.start], t[:, cols.stop:]]
+    if materials:
+        parts.append(sc.lobe_mask[:, None].astype(np.float32))
+    return np.concatenate(parts, axis=1).tobytes()
 
 
 def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_bounces: int, init: float,
-                device: torch.device, seed: int = 7, target_chunk: int = 16, first_index: int = 0) -> List[SceneTask]:
+                device: torch.device, seed: int = 7, target_chunk: int = 16, first_index: int = 0,
+                learn: Sequence[str] = ("kd",), init_ks: float = 0.5, init_ke: float = 5.0) -> List[SceneTask]:
     """Load the scenes (one device geometry per distinct geometry), render the
     targets in batches of `target_chunk`, and create the parameters.  files[i]
     is global scene first_index + i: its target render traces the samples of
-    seed + 10^9 + (first_index + i) * W*H*target_spp, whichever rank loads it."""
+    seed + 10^9 + (first_index + i) * W*H*target_spp, whichever rank loads it.
+
+    learn with "ks" / "ke" (MaterialOptimizer's): scenes that differ only in
+    the values of Kd, Ks, Ke share one geometry handle; the tasks carry ks, ke
+    and their truths, the learned blocks start at init / init_ks / init_ke on
+    the rows they act on (lobe rows, emitter rows) and the others at the truth;
+    the targets are rendered with the true values of all three."""
+    if set(learn) - set(_BLOCKS) or not tuple(learn):
+        raise ValueError("learn must name some of %s, got %r" % (_BLOCKS, tuple(learn)))
+    learn = tuple(b for b in _BLOCKS if b in tuple(learn))
+    mats = learn != ("kd",)
     groups = {}  # geometry key -> device Scene
     tasks = []
     for k, f in enumerate(files):
         host = Scene.from_file(f, device=False)
-        key = _geometry_key(host)
+        key = _geometry_key(host, mats)
         if key not in groups:
             groups[key] = Scene.from_file(f)
         truth = torch.tensor(host.materials, device=device)
+        kd0 = torch.full_like(truth, init) if "kd" in learn else truth.clone()
+        task = SceneTask(f, groups[key], truth, None, kd0.requires_grad_("kd" in learn), index=first_index + k)
+        if mats:
+            _, ks, ke, _ = host.material_params()
+            lobe = torch.tensor(host.lobe_mask, device=device)[:, None].float().expand(-1, 3)
+            emit = torch.tensor(host.emitter_mask, device=device)[:, None].float().expand(-1, 3)
+            task.truth_ks, task.truth_ke = torch.tensor(ks, device=device), torch.tensor(ke, device=device)
+            task.ks = (lobe * init_ks).requires_grad_(True) if "ks" in learn else task.truth_ks.clone()
+            task.ke = (emit * init_ke).requires_grad_(True) if "ke" in learn else task.truth_ke.clone()
         host.close()
-        tasks.append(SceneTask(f, groups[key], truth, None, torch.full_like(truth, init).requires_grad_(True),
-                               index=first_index + k))
+        tasks.append(task)
     stride = width * height * target_spp
     with torch.no_grad():
         for sc in groups.values():
             mine = [i for i, t in enumerate(tasks) if t.scene is sc]
             for idx in _runs(mine, tasks, target_chunk):
                 kd = torch.stack([tasks[i].truth for i in idx])
-                img = torch_ops.render_batch(sc, kd, width, height, target_spp, max_bounces,
-                                             seed=seed + 10**9 + tasks[idx[0]].index * stride, seed_stride=stride)
+                s0 = seed + 10**9 + tasks[idx[0]].index * stride
+                if mats:
+                    img = torch_ops.render_materials_batch(sc, kd, torch.stack([tasks[i].truth_ks for i in idx]),
+                                                           torch.stack([tasks[i].truth_ke for i in idx]), width,
+                                                           height, target_spp, max_bounces, seed=s0,
+                                                           seed_stride=stride)
+                else:
+                    img = torch_ops.render_batch(sc, kd, width, height, target_spp, max_bounces, seed=s0,
+                                                 seed_stride=stride)
                 for j, i in enumerate(idx):
                     tasks[i].target = img[j].clone()
     return tasks
@@ -136,12 +186,28 @@ class MaterialOptimizer:
     adjoint n_total frames later -- so each rank of a scene-parallel split
     traces exactly the one-rank run's samples for its scenes.  A batch is
     one geometry's tasks with consecutive global indices (seed_stride = one
-    frame between its sets)."""
+    frame between its sets).
+
+    learn: the blocks to optimise, a subset of ("kd", "ks", "ke"); the default
+    ("kd",) is the Kd-only optimiser above.  With "ks" and/or "ke" a batch
+    holds one (S, nT, 3) leaf per learned block (the tasks' kd / ks / ke become
+    views of their rows; the other blocks stay at the tasks' values, None = the
+    geometry handle's own) and renders through
+    torch_ops.render_materials_batch: one batched forward and one batched
+    material-adjoint launch per step, on the same sample streams.  Rows the
+    blocks do not act on are masked (scene.lobe_mask for Ks, scene.emitter_mask
+    for Ke: structure is frozen at load); Kd and Ks are clamped to [0, 1], Ke to
+    [0, inf).  `lr` may then be a dict per block, e.g. {"ks": 0.02, "ke":
+    0.2} (emission lives on another scale).  tie_shared is a Kd-only feature."""
 
     def __init__(self, tasks: List[SceneTask], width: int, height: int, spp: int, max_bounces: int,
-                 lr: float = 1e-2, tie_shared: Optional[int] = None, seed: int = 0, flush_every: int = 16,
-                 decorrelate: bool = True, n_total: Optional[int] = None):
+                 lr: Union[float, Dict[str, float]] = 1e-2, tie_shared: Optional[int] = None, seed: int = 0,
+                 flush_every: int = 16, decorrelate: bool = True, n_total: Optional[int] = None,
+                 learn: Sequence[str] = ("kd",)):
         self.tasks, self.W, self.H, self.spp, self.mb = tasks, width, height, spp, max_bounces
+        if not tuple(learn) or set(learn) - set(_BLOCKS):
+            raise ValueError("learn must name some of %s, got %r" % (_BLOCKS, tuple(learn)))
+        self.learn = tuple(b for b in _BLOCKS if b in tuple(learn))
         self.tie, self.seed, self.flush_every, self.decorrelate = tie_shared, seed, flush_every, decorrelate
         # the job's scene count: the caller's, else max(index) + 1 (a rank
         # given only the tasks of global scenes b .. b+k-1 must pass the job's n)
@@ -160,6 +226,14 @@ class MaterialOptimizer:
             else:
                 self.batches.append((t.scene, [t]))
         self.leaves, self.targets, self.offsets = [], [], []
+        self.shared = None
+        self.step_count = 0
+        self.pending = []  # (tasks, per-scene loss tensor) in step order
+        if self.learn != ("kd",):
+            self._init_materials(lr, tie_shared)
+            return
+        if isinstance(lr, dict):
+            lr = lr["kd"]
         for sc, ts in self.batches:
             leaf = torch.stack([t.kd.detach() for t in ts]).clone().requires_grad_(True)
             tgt = torch.stack([t.target for t in ts])
@@ -168,17 +242,75 @@ class MaterialOptimizer:
             self.offsets.append(ts[0].index)  # global index of the batch's first scene
             self.leaves.append(leaf)
             self.targets.append(tgt)
-        self.shared = None
         if tie_shared:
             self.shared = tasks[0].kd.detach()[:tie_shared].clone().requires_grad_(True) if tasks else \
                 torch.full((tie_shared, 3), 0.5, device="cuda", requires_grad=True)
         self.params = self.leaves + ([self.shared] if self.shared is not None else [])
         self.opt = torch.optim.Adam(self.params, lr=lr)
-        self.step_count = 0
-        self.pending = []  # (tasks, per-scene loss tensor) in step order
+
+    def _init_materials(self, lr, tie_shared):
+        """learn with "ks" / "ke": per batch, one leaf per learned block and the fixed (S, nT, 3) values (or
+        None) of the others; self.leaves[i] is the dict block -> leaf of batch i."""
+        if tie_shared:
+            raise ValueError("MaterialOptimizer: tie_shared is supported for learn=('kd',) only")
+        self.fixed, self.masks = [], []
+        for sc, ts in self.batches:
+            leaf, fixed = {}, {}
+            for b in _BLOCKS:
+                vals = [getattr(t, b) for t in ts]
+                if b in self.learn:
+                    if any(v is None for v in vals):
+                        raise ValueError("MaterialOptimizer: learn has %r but a task carries no %s "
+                                         "(build_tasks(learn=...))" % (b, b))
+                    leaf[b] = torch.stack([v.detach() for v in vals]).clone().requires_grad_(True)
+                    for j, t in enumerate(ts):
+                        setattr(t, b, leaf[b][j])
+                else:
+                    fixed[b] = None if any(v is None for v in vals) else torch.stack([v.detach() for v in vals])
+            tgt = torch.stack([t.target for t in ts])
+            for j, t in enumerate(ts):
+                t.target = tgt[j]
+            dev = tgt.device
+            self.masks.append({"ks": torch.tensor(sc.lobe_mask, device=dev)[None, :, None].float(),
+                               "ke": torch.tensor(sc.emitter_mask, device=dev)[None, :, None].float()})
+            self.offsets.append(ts[0].index)
+            self.leaves.append(leaf)
+            self.fixed.append(fixed)
+            self.targets.append(tgt)
+        rate = lr if isinstance(lr, dict) else {b: lr for b in self.learn}
+        groups = [{"params": [leaf[b] for leaf in self.leaves], "lr": rate[b]} for b in self.learn]
+        self.params = [q for g in groups for q in g["params"]]
+        self.opt = torch.optim.Adam([g for g in groups if g["params"]] or [{"params": []}])
+
+    def _step_materials(self):
+        self.opt.zero_grad(set_to_none=False)
+        step, T = self.step_count, self.n_total
+        for (sc, ts), leaf, fixed, mask, target, n_before in zip(self.batches, self.leaves, self.fixed, self.masks,
+                                                                 self.targets, self.offsets):
+            v = {b: leaf[b] if b in leaf else fixed[b] for b in _BLOCKS}
+            for b in ("ks", "ke"):  # frozen rows: no value, no gradient
+                if b in leaf:
+                    v[b] = leaf[b] * mask[b]
+            base = self.seed + (2 * step * T + n_before) * self.frame
+            img = torch_ops.render_materials_batch(
+                sc, v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, self.mb, seed=base, seed_stride=self.frame,
+                adjoint_seed=(base + T * self.frame) if self.decorrelate else None)
+            per_scene = ((img - target) ** 2).mean(dim=(1, 2, 3))
+            per_scene.sum().backward()
+            self.pending.append((ts, per_scene.detach()))
+        self.opt.step()
+        with torch.no_grad():
+            for leaf in self.leaves:
+                for b, q in leaf.items():
+                    q.clamp_(0.0, None if b == "ke" else 1.0)  # emission has no upper bound
+        self.step_count += 1
+        if self.flush_every and self.step_count % self.flush_every == 0:
+            _flush_losses(self.pending)
 
     def step(self):
         """One Adam step over every scene (no host synchronisation)."""
+        if self.learn != ("kd",):
+            return self._step_materials()
         self.opt.zero_grad(set_to_none=False)
         step = self.step_count
         for (sc, ts), leaf, target, n_before in zip(self.batches, self.leaves, self.targets, self.offsets):

@@ -300,6 +300,40 @@ class Scene:
                                              g.ctypes.data_as(N.dp)), "adjoint_materials")
         return g[0], g[1], g[2]
 
+    def adjoint_materials_batch(self, adj, kd, ks, ke, width, height, spp, max_bounces, seed=0, seed_stride=None,
+                                row_begin=0, row_end=None, row_step=1):
+        """``adjoint_materials`` for S material sets in ONE batched launch
+        (ipt_adjoint_mat_batch_dev): adj is (S, H, W, 3) full frames, kd / ks /
+        ke are (S, nT, 3) host arrays or None (the scene's own values in every
+        set); set b traces seed + b * seed_stride (default: one frame of
+        samples).  Returns (S, 3, nT, 3) float64, [set][Kd | Ks | Ke].  torch
+        only provides the device memory."""
+        import torch
+
+        adj = np.ascontiguousarray(np.asarray(adj, np.float32))
+        if adj.ndim != 4 or adj.shape[1:] != (height, width, 3):
+            raise ValueError("adj must be (S, H=%d, W=%d, 3), got %s" % (height, width, adj.shape))
+        S = adj.shape[0]
+        dev = []
+        for name, v in (("kd", kd), ("ks", ks), ("ke", ke)):
+            if v is None:
+                dev.append(None)
+                continue
+            v = np.ascontiguousarray(np.asarray(v, np.float32))
+            if v.shape != (S, self.nT, 3):
+                raise ValueError("%s must be (S=%d, nT=%d, 3), got %s" % (name, S, self.nT, v.shape))
+            dev.append(torch.from_numpy(v).cuda())
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        a = torch.from_numpy(adj).cuda()
+        g = torch.zeros((S, 3, self.nT, 3), device=a.device, dtype=torch.float64)
+        ptr = [None if t is None else t.data_ptr() for t in dev]
+        N.check(N.lib().ipt_adjoint_mat_batch_dev(self.handle, C.byref(p), S, stride, ptr[0], ptr[1], ptr[2],
+                                                  a.data_ptr(), g.data_ptr(),
+                                                  torch.cuda.current_stream(a.device).cuda_stream),
+                "adjoint_materials_batch")
+        return g.cpu().numpy()
+
     def graph(self, target, width, height, spp, max_bounces=None, seed=0, row_begin=0, row_end=None, row_step=1):
         """createGraph: returns (acc[(nT+1)*nT, 8] float64, data[(nT+1)*nT*7] float32)."""
         p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)

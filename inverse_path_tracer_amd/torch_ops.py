@@ -100,7 +100,8 @@ def render(scene: Scene, kd: torch.Tensor, width: int, height: int, spp: int, ma
     return _RenderFn.apply(kd, scene, p, adjoint_seed)
 
 
-BATCH_REFUSED = "material adjoint: the scene batch (n_scenes > 1) is not supported"
+BATCH_REFUSED = ("material adjoint: the scene batch (n_scenes > 1) is not supported by render_materials; "
+                 "pass (S, nT, 3) tensors to render_materials_batch")
 
 
 def _ptr(t):
@@ -146,7 +147,8 @@ def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int
     load: ke rows outside ``scene.emitter_mask`` and ks rows outside
     ``scene.lobe_mask`` are ignored, and their gradients are exactly 0; the
     Phong exponent is not differentiated.  Refused (NativeError): the
-    unbounded estimator (max_bounces None) and batched inputs (S, nT, 3).
+    unbounded estimator (max_bounces None) and batched inputs (S, nT, 3),
+    which ``render_materials_batch`` takes.
     `adjoint_seed` as in ``render``."""
     given = [t for t in (kd, ks, ke) if t is not None]
     if not given:
@@ -161,6 +163,61 @@ def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int
                             "give max_bounces in 0..62")
     p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
     return _RenderMaterialsFn.apply(kd, ks, ke, scene, p, adjoint_seed)
+
+
+class _RenderMaterialsBatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kd, ks, ke, scene, params, stride, adjoint_seed):
+        given = [t for t in (kd, ks, ke) if t is not None]
+        dev, S = given[0].device, given[0].shape[0]
+        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
+        hdr = torch.empty((S, params.height, params.width, 3), device=dev, dtype=torch.float32)
+        N.check(N.lib().ipt_render_mat_batch_dev(scene.handle, C.byref(params), S, stride, _ptr(c[0]), _ptr(c[1]),
+                                                 _ptr(c[2]), hdr.data_ptr(), _stream(dev)),
+                "ipt_render_mat_batch_dev")
+        ctx.scene, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat, ctx.S = scene, params, stride, adjoint_seed, c, S
+        return hdr
+
+    @staticmethod
+    def backward(ctx, grad_hdr):
+        p = _replay_params(ctx.params, ctx.adjoint_seed)
+        kd, ks, ke = ctx.mat
+        adj = grad_hdr.float().contiguous()
+        g = torch.zeros((ctx.S, 3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
+        N.check(N.lib().ipt_adjoint_mat_batch_dev(ctx.scene.handle, C.byref(p), ctx.S, ctx.stride, _ptr(kd), _ptr(ks),
+                                                  _ptr(ke), adj.data_ptr(), g.data_ptr(), _stream(adj.device)),
+                "ipt_adjoint_mat_batch_dev")
+        out = [g[:, i].float() if (t is not None and ctx.needs_input_grad[i]) else None
+               for i, t in enumerate((kd, ks, ke))]
+        return out[0], out[1], out[2], None, None, None, None
+
+
+def render_materials_batch(scene: Scene, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4,
+                           seed: int = 0, seed_stride=None, adjoint_seed=None) -> torch.Tensor:
+    """``render_materials`` for S material sets over one geometry: kd, ks, ke
+    are (S, nT, 3) CUDA tensors (any may be None = the scene's own values in
+    every set, or not require grad; at least one is given and all share S)
+    -> HDR images (S, H, W, 3).  ONE batched forward launch
+    (ipt_render_mat_batch_dev); the backward is ONE batched launch of the
+    material adjoint.  Set b is ``render_materials`` of its rows with seed
+    ``seed + b * seed_stride`` bit for bit (default stride: one frame of
+    samples, as ``render_batch``).  Masks, refusals and `adjoint_seed` as in
+    ``render_materials``."""
+    given = [t for t in (kd, ks, ke) if t is not None]
+    if not given:
+        raise ValueError("render_materials_batch needs at least one of kd, ks, ke as a device tensor")
+    for t in given:
+        if t.dim() != 3 or tuple(t.shape[1:]) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (S, nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+        if t.shape[0] != given[0].shape[0]:
+            raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
+                             [tuple(u.shape) for u in given])
+    if max_bounces is None or max_bounces < 0:
+        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; "
+                            "give max_bounces in 0..62")
+    stride = width * height * spp if seed_stride is None else int(seed_stride)
+    p = N.make_params(width, height, spp, max_bounces, seed)
+    return _RenderMaterialsBatchFn.apply(kd, ks, ke, scene, p, stride, adjoint_seed)
 
 
 class _BatchRenderFn(torch.autograd.Function):
