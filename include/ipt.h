@@ -237,10 +237,25 @@ int ipt_render_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, 
 /* d(sum adj*I)/d(Kd, Ks, Ke) of the bounded estimator in one launch:
  * grad_dev is 3*nT*3 doubles, [Kd | Ks | Ke], ACCUMULATED (zero it first).
  * The Kd block equals ipt_adjoint_dev's.  Refused with an error:
- * max_bounces < 0 (the unbounded estimator) and max_bounces > 62. */
+ * max_bounces < 0 (the unbounded estimator: ipt_adjoint_mat_unbounded_dev
+ * below) and max_bounces > 62. */
 int ipt_adjoint_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
                         const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
 int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj /*H*W*3*/, double *grad /*3*nT*3*/);
+/* The same for the reference's own estimator (max_bounces = -1: no bounce cap,
+ * Russian roulette at 0.9), whose forward is ipt_render_mat_dev with
+ * max_bounces = -1: one launch of the unbounded adjoint's ring-and-replay
+ * sweep, emitting all three blocks.  grad_dev as above (3*nT*3 doubles,
+ * [Kd | Ks | Ke], ACCUMULATED); the Kd block equals ipt_adjoint_dev's at
+ * max_bounces = -1; p's row band and row_step are honoured.  One material
+ * set.  Refused with an error before anything is enqueued: max_bounces >= 0
+ * (ipt_adjoint_mat_dev is the bounded call), a host-only scene, more than
+ * 65535 triangles, LDS tables that leave no room for one record slot per lane
+ * within 160 KiB.  (Additive symbols: ipt_abi_version stays 5.) */
+int ipt_adjoint_mat_unbounded_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                                  const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
+int ipt_adjoint_mat_unbounded_host(void *scene, const ipt_params_t *p, const float *adj /*H*W*3*/,
+                                   double *grad /*3*nT*3*/);
 /* The scene batch of the two, with ipt_render_batch_dev's conventions:
  * n_scenes material sets over one geometry in one launch, set b with seed
  * p->seed + b*seed_stride.  kd_dev / ks_dev / ke_dev: n_scenes*nT*3 floats

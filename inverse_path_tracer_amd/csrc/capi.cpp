@@ -481,6 +481,26 @@ int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj, d
   return gpu_status(ipt::gpu_adjoint_mat_host(s, to_params(p), adj, grad));
 }
 
+int ipt_adjoint_mat_unbounded_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                                  const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !adj_dev || !grad_dev) {
+    if (s) fail("ipt_adjoint_mat_unbounded_dev: bad arguments (params, adj_dev and grad_dev are required)");
+    return -1;
+  }
+  return gpu_status(
+      ipt::gpu_adjoint_mat_unbounded(s, to_params(p), kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream));
+}
+
+int ipt_adjoint_mat_unbounded_host(void *scene, const ipt_params_t *p, const float *adj, double *grad) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !adj || !grad) {
+    if (s) fail("ipt_adjoint_mat_unbounded_host: bad arguments (params, adj and grad are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_adjoint_mat_unbounded_host(s, to_params(p), adj, grad));
+}
+
 int ipt_render_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, uint64_t seed_stride, const float *kd_dev,
                          float *hdr_dev, void *stream) {
   GpuScene *s = as_scene(scene);

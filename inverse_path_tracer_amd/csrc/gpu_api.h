@@ -51,6 +51,11 @@ int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, cons
 int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
                     const float *adj_dev, double *grad_dev, void *stream);
 int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad);
+// The same three blocks for the unbounded estimator (max_bounces < 0; one launch of
+// trace_matu_kernel).  Refuses max_bounces >= 0 and the scene batch.
+int gpu_adjoint_mat_unbounded(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                              const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
+int gpu_adjoint_mat_unbounded_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad);
 // The scene batch of the two (p.nscenes sets, p.seed_stride): kd / ks / ke are n_scenes*nT*3
 // (nullptr = the scene's own values in every set); hdr_dev n_scenes images, grad_dev
 // n_scenes x 3 x nT x 3 doubles [set][Kd | Ks | Ke], accumulated.  Set b is the single-set

@@ -121,6 +121,13 @@ __host__ __device__ inline size_t graph_lds_doubles(int nT, int nE) {
 __host__ __device__ inline size_t mat_lds_doubles(int grad_slots, int nE, bool spec) {
   return (size_t)grad_slots * 3 * (spec ? 2 : 1) + (size_t)(nE > 0 ? nE : 0) * 3;
 }
+// The unbounded material adjoint's brute-force instances keep the owner
+// lane's carried state (Scar, Mlo, the first triangle, the work item) in LDS:
+// words per lane, in front of the owner markers (trace_body.h, kCarryLds).
+constexpr int kCarryWords = 9;
+__host__ __device__ inline size_t mat_carry_bytes(bool bvh) {
+  return bvh ? 0 : (size_t)kCarryWords * kBlock * sizeof(uint32_t);
+}
 constexpr int kMaxAdjBounces = 62;
 // ADJU ring slots per lane (3 words each, like ADJ's records: tri | et,
 // emitter factor, coeff; the prefix throughputs are rebuilt by the sweep's
@@ -796,6 +803,26 @@ trace_mat_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const Tr
 #include "trace_body.h"
 }
 
+// The unbounded material adjoint: MODE_ADJU's tracing, ring
+// and replays with the material sweep.  Its owner lanes carry the path's first
+// triangle across replays (trace_body.h, kTri0Carry).  A __global__ of its
+// own, so trace_kernel's and trace_mat_kernel's instances stay what they were;
+// bounds as the unbounded adjoint's.
+template <bool SPEC, bool BVH>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
+                          amdgpu_waves_per_eu(min_blocks<MODE_ADJU, BVH>()))) void
+trace_matu_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+                  const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat, const float *__restrict__ kd,
+                  const int *__restrict__ emit_tri, const float *__restrict__ emit_cdf,
+                  const float *__restrict__ emit_pmf, float *__restrict__ out_samples, const float *__restrict__ adj,
+                  double *__restrict__ grad, const uint8_t *__restrict__ target, double *__restrict__ edges,
+                  const int *__restrict__ tri_emit) {
+  constexpr int MODE = MODE_ADJU;
+  constexpr bool MATG = true;
+  constexpr bool MATB = false;
+#include "trace_body.h"
+}
+
 // Per-launch TriMat tables of the material overrides (stream scratch): the
 // scene's entries with ks / ke replaced from nT*3 device arrays (nullptr: the
 // scene's own); flags and shininess are kept, and rows outside the lobe /
@@ -949,16 +976,18 @@ struct GpuScene {
   int accel = IPT_ACCEL_AUTO;
   size_t adju_base = 0;  // gpu_adjoint's choice of LDS ring slots (unbounded, brute force) ...
   int adju_nl = 0;       // ... made for this LDS base
+  size_t matu_base = 0;  // gpu_adjoint_mat_unbounded's own choice (trace_matu_kernel's occupancy) ...
+  int matu_nl = 0;       // ... for its LDS base
   int *grad_map = nullptr, *slot_tri = nullptr;  // ADJ hot-set LDS slots (large scenes)
   int *tri_emit = nullptr;  // triangle -> emitter index or -1 (material overrides and adjoint)
   // slots 0..23: trace_kernel<mode, spec, bvh>; 24..27: trace_mat_kernel<spec, bvh>;
-  // 28..35: trace_fwd_mat_kernel<FWD | FWDM, spec, bvh> (inst_slot)
-  int grid[36] = {0};       // resident workgroups per instance (0 = not queried)
-  size_t grid_lds[36] = {0};
-  size_t pick_base[36] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
-  size_t pick_tail[36] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
-  int pick_opt[36] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  // 28..35: trace_fwd_mat_kernel<FWD | FWDM, spec, bvh>; 36..39: trace_matu_kernel<spec, bvh> (inst_slot)
+  int grid[40] = {0};       // resident workgroups per instance (0 = not queried)
+  size_t grid_lds[40] = {0};
+  size_t pick_base[40] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
+  size_t pick_tail[40] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
+  int pick_opt[40] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
+                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   // dynamic-chunk counters per stream (stream_counters): `words` grab words,
   // zeroed once; every launch leaves them zero (TraceArgs::chunk_ctr)
   struct Counters {
@@ -1164,14 +1193,22 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 #ifndef IPT_DEBUG_GRID
 #define IPT_DEBUG_GRID 0
 #endif
-// The kernel a launch runs: trace_kernel<MODE, SPEC, BVH>, or (MODE_ADJ only)
-// the material adjoint trace_mat_kernel<SPEC, BVH>, or (the forwards only) the
-// batch forward with per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
+// The kernel a launch runs: trace_kernel<MODE, SPEC, BVH>, or the material
+// adjoint (MODE_ADJ: trace_mat_kernel<SPEC, BVH>, MODE_ADJU: the unbounded
+// trace_matu_kernel<SPEC, BVH>), or (the forwards only) the batch forward with
+// per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
 enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2 };
+// The material adjoint's kernel for MODE (KIND_MATG).
+template <int MODE, bool SPEC, bool BVH>
+constexpr auto matg_kernel() {
+  static_assert(MODE == MODE_ADJ || MODE == MODE_ADJU, "the material adjoint is MODE_ADJ or MODE_ADJU");
+  if constexpr (MODE == MODE_ADJU) return &trace_matu_kernel<SPEC, BVH>;
+  else return &trace_mat_kernel<SPEC, BVH>;
+}
 // An instance's slot in GpuScene's per-instance caches.
 template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr int inst_slot() {
-  return (KIND == KIND_MATG   ? 24
+  return (KIND == KIND_MATG   ? (MODE == MODE_ADJU ? 36 : 24)
           : KIND == KIND_FWDB ? 28 + (MODE == MODE_FWDM ? 4 : 0)
                               : MODE * 4) +
          (SPEC ? 2 : 0) + (BVH ? 1 : 0);
@@ -1182,7 +1219,7 @@ static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
   if (s->grid[slot] == 0 || s->grid_lds[slot] != lds_bytes) {
     int per_cu = 0, cus = 0;
     if constexpr (KIND == KIND_MATG) {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_mat_kernel<SPEC, BVH>, kBlock, lds_bytes));
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, matg_kernel<MODE, SPEC, BVH>(), kBlock, lds_bytes));
     } else if constexpr (KIND == KIND_FWDB) {
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, BVH>, kBlock,
                                                            lds_bytes));
@@ -1199,7 +1236,7 @@ static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
     s->grid_lds[slot] = lds_bytes;
     if (IPT_DEBUG_GRID)  // (make variant DEFS=-DIPT_DEBUG_GRID=1)
       std::fprintf(stderr, "[ipt] %s<%d,%d,%d>: %zu B LDS/block, %d blocks/CU x %d CUs\n",
-                   KIND == KIND_MATG   ? "trace_mat_kernel"
+                   KIND == KIND_MATG   ? (MODE == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
                    : KIND == KIND_FWDB ? "trace_fwd_mat_kernel"
                                        : "trace_kernel",
                    MODE, (int)SPEC, (int)BVH, lds_bytes, per_cu, cus);
@@ -1516,7 +1553,7 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float 
   }
   const TriMat *mat = mat_dev ? mat_dev : s->mat;
   if constexpr (KIND == KIND_MATG)
-    hipLaunchKernelGGL((trace_mat_kernel<SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs, s->geom,
+    hipLaunchKernelGGL((matg_kernel<MODE, SPEC, BVH>()), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs, s->geom,
                        mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad, target,
                        edges, s->tri_emit);
   else if constexpr (KIND == KIND_FWDB)
@@ -1561,7 +1598,7 @@ static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) 
       if (l > 160 * 1024) continue;
       int per_cu = 0;
       if constexpr (KIND == KIND_MATG) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_mat_kernel<SPEC, true>, kBlock, l));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, matg_kernel<MODE, SPEC, true>(), kBlock, l));
       } else if constexpr (KIND == KIND_FWDB) {
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, true>, kBlock, l));
       } else {
@@ -1856,7 +1893,7 @@ int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev
   if (check_params(s, p) || check_sets(p.nscenes)) return -1;
   // the forward's own bounce limit is the adjoint's: one contract for the pair
   if (p.max_bounces < 0 || p.max_bounces > kMaxAdjBounces) {
-    gpu_set_error("material batch: give max_bounces in 0..62 (the unbounded estimator is not supported)");
+    gpu_set_error("material batch: give max_bounces in 0..62 (the unbounded estimator is not supported; one material set: ipt_adjoint_mat_unbounded_dev)");
     return -1;
   }
   if (s->host.nT > kMaxAdjTris) {
@@ -1892,7 +1929,7 @@ int gpu_adjoint_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_de
 static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
                             const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
   if (p.max_bounces < 0) {
-    gpu_set_error("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; give max_bounces in 0..62");
+    gpu_set_error("material adjoint: the unbounded estimator (max_bounces < 0) is not supported here; give max_bounces in 0..62, or call ipt_adjoint_mat_unbounded_dev (one material set)");
     return -1;
   }
   if (p.max_bounces > kMaxAdjBounces) {
@@ -1927,6 +1964,85 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
   if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
   return launch<MODE_ADJ, KIND_MATG>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream, 0,
                                 mat);
+}
+
+// dL/dKd, dL/dKs, dL/dKe of the reference's own estimator (no bounce cap) in
+// one launch of trace_matu_kernel: gpu_adjoint's unbounded
+// launch with the material adjoint's bins, overrides and tri_emit map.
+// grad_dev as gpu_adjoint_mat's.  One material set.
+static int check_unbounded(const RenderParams &p) {
+  if (p.max_bounces >= 0) {
+    gpu_set_error("unbounded material adjoint: max_bounces must be -1 (no bounce cap); ipt_adjoint_mat_dev takes max_bounces in 0..62");
+    return -1;
+  }
+  return 0;
+}
+int gpu_adjoint_mat_unbounded(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
+                              const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+  if (check_unbounded(p) || check_params(s, p)) return -1;
+  if (p.nscenes > 1) {
+    gpu_set_error("unbounded material adjoint: the scene batch (n_scenes > 1) is not supported");
+    return -1;
+  }
+  if (s->host.nT > kMaxAdjTris) {
+    gpu_set_error("adjoint supports at most 65535 triangles");
+    return -1;
+  }
+  TraceArgs a = make_args(s, p);
+  a.sample_major = IPT_ADJ_PIXEL_MAJOR ? 0 : 1;
+  if (s->grad_map) {
+    a.grad_slots = kLdsGradBytes / (3 * (int)sizeof(double));
+    a.grad_map = s->grad_map;
+    a.slot_tri = s->slot_tri;
+  } else {
+    a.grad_slots = s->host.nT;
+  }
+  const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
+  const size_t per = fields * kBlock * sizeof(float);  // one ring slot per lane
+  const bool bvh = use_bvh(s);
+  // bins (Kd, Ks with a lobe, Ke per emitter) + tables + the owners' carried words + owner markers
+  const size_t base = mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
+                      mat_carry_bytes(bvh) + (size_t)kBlock * sizeof(uint32_t);
+  // ring slots in LDS, chosen as gpu_adjoint chooses them but for THIS
+  // kernel's occupancy and in a cache of its own (matu_base / matu_nl): the
+  // bins are larger than the Kd-only adjoint's, so the count may differ
+  a.rec_cap = kAdjuRing;
+  int nl = bvh ? IPT_ADJU_LDS_SLOTS_BVH : IPT_ADJU_LDS_SLOTS;
+  if (IPT_ADJU_LDS_SLOTS_FIXED >= 0) {
+    nl = IPT_ADJU_LDS_SLOTS_FIXED;
+  } else if (!bvh && base + per <= 160 * 1024) {
+    if (s->matu_base != base) {
+      auto occ = [&](size_t bytes, int *o) {
+        return s->has_ks ? hipOccupancyMaxActiveBlocksPerMultiprocessor(o, trace_matu_kernel<true, false>, kBlock, bytes)
+                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(o, trace_matu_kernel<false, false>, kBlock, bytes);
+      };
+      int occ0 = 0, best = 0;
+      HIP_TRY(occ(base, &occ0));
+      for (int k = nl; k > 0 && best == 0; --k) {
+        int o = 0;
+        HIP_TRY(occ(base + k * per, &o));
+        if (o >= occ0 && base + k * per <= IPT_ADJU_LDS_CAP) best = k;
+      }
+      s->matu_base = base;
+      s->matu_nl = best;
+    }
+    nl = s->matu_nl;
+  }
+  if (g_adju_lds.load() > 0) nl = g_adju_lds.load();
+  a.rec_lds = std::max(1, std::min(nl, kAdjuRing - 1));  // (>= 1: see gpu_adjoint)
+  // a forced or default count the base leaves no room for shrinks to what fits
+  // (>= 1); a base with no room for one slot per lane is refused
+  if (base + per > 160 * 1024) {
+    gpu_set_error("unbounded material adjoint: the Kd/Ks/Ke bins and the scene's LDS tables plus one record slot per lane exceed 160 KiB");
+    return -1;
+  }
+  a.rec_lds = (int)std::min<size_t>((size_t)a.rec_lds, (160 * 1024 - base) / per);
+  const size_t lds = base + (size_t)a.rec_lds * per;
+  StreamScratch tab;
+  const TriMat *mat = nullptr;
+  if (pack_materials(s, ks_dev, ke_dev, 1, (hipStream_t)stream, tab, &mat)) return -1;
+  return launch<MODE_ADJU, KIND_MATG>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream,
+                                      0, mat);
 }
 
 // Bounded adjoint launches of at least this many samples (all material sets)
@@ -2371,6 +2487,19 @@ int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, d
   HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
   if (gpu_adjoint_mat(s, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
+  HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int gpu_adjoint_mat_unbounded_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad) {
+  if (check_unbounded(p) || check_params(s, p)) return -1;
+  const size_t na = (size_t)p.width * p.height * 3, ng = (size_t)s->host.nT * 9;
+  DevBuf a, g;
+  HIP_TRY(hipMalloc(&a.p, na * sizeof(float)));
+  HIP_TRY(hipMalloc(&g.p, ng * sizeof(double)));
+  HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
+  if (gpu_adjoint_mat_unbounded(s, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
   HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }

@@ -4,8 +4,9 @@
 // force-inlined function template taking the launch arguments changed the
 // register allocation and scratch of the BVH instances of trace_kernel.
 // The including kernel provides, as template parameters or constexpr locals,
-// MODE, SPEC, BVH and MATG (the material adjoint: the bounded adjoint whose
-// sweep also emits dL/dKs and dL/dKe) and MATB (a forward whose
+// MODE, SPEC, BVH and MATG (the material adjoint: an adjoint -- bounded,
+// DESIGN.md §13, or unbounded, §16 -- whose sweep also emits dL/dKs and
+// dL/dKe) and MATB (a forward whose
 // scene batch has one TriMat table per set), the parameters of
 // TraceKernArgs under their names, and tri_emit (MATG: triangle -> emitter
 // index or -1; nullptr otherwise).
@@ -99,6 +100,16 @@
   if (po)
     for (int i = tid; i < nT * nE; i += nthr) lds_po[i] = a.pomask[i];
   float *lds_rec = a.small_pairs ? reinterpret_cast<float *>(lds_po) + (po ? nT * nE : 0) : lds_e3;
+  // the unbounded material adjoint, brute force (96 VGPRs): the owner lane's
+  // carried state -- Scar, Mlo, the path's first triangle and the work item,
+  // each touched once per chunk -- in kCarryWords LDS words per lane instead of registers
+  // (mat_carry_bytes on the host side)
+  constexpr bool kCarryLds = MATG && MODE == MODE_ADJU && !BVH;
+  lds_u32 *carry_ws = nullptr;
+  if (kCarryLds) {
+    carry_ws = (lds_u32 *)lds_rec;
+    lds_rec += kCarryWords * kBlock;
+  }
   // MODE_ADJ: one word per lane (the sweep's owner markers) in front of the
   // vertex records
   if (is_adj<MODE>()) lds_rec += kBlock;
@@ -254,6 +265,32 @@
   // starting at vertex 0; captured while a replay passes its start)
   V3 Scar = mk(0.f, 0.f, 0.f), Mlo = mk(1.f, 1.f, 1.f);
   int rhi = 0, rslot = 0;
+  // the unbounded material adjoint: the path's first triangle, kept by its
+  // owner lane across the replays (every replay passes vertex 0 again and
+  // captures the same triangle) -- a replay chunk does not start at vertex 0,
+  // so the sweep cannot read it from the chunk's first task
+  constexpr bool kTri0Carry = MATG && MODE == MODE_ADJU;
+  static_assert(!kTri0Carry || kSub == 0, "the unbounded material adjoint has no sub-chunked sweep (IPT_ADJU_SUB)");
+  int tri0_r = 0;
+  // carried state in LDS (kCarryLds): word f of lane l at carry_ws[f * kBlock + l];
+  // 0-2 Scar, 3-5 Mlo, 6 tri_0, 7-8 the work item.  Written by the owner lane,
+  // read by its task lanes (same wave: LDS operations of a wave complete in
+  // order).  The lane index is opaque at each use, so that the addresses are
+  // formed there and not kept in registers through the trace loop.
+  auto carry_at = [&](int f, int l) -> lds_u32 * {
+    asm volatile("" : "+v"(l));
+    return carry_ws + f * kBlock + l;
+  };
+  auto carry_put3 = [&](int f, V3 v) {
+    lds_f32 *w = (lds_f32 *)carry_at(f, tid);
+    w[0] = v.x;
+    w[kBlock] = v.y;
+    w[2 * kBlock] = v.z;
+  };
+  auto carry_get3 = [&](int f, int l) -> V3 {  // of lane l of this wave
+    const lds_f32 *w = (const lds_f32 *)carry_at(f, (tid & ~63) + l);
+    return mk(w[0], w[kBlock], w[2 * kBlock]);
+  };
   // IPT_ADJU_SUB: the end of the sub-chunk this lane sweeps next (0: none);
   // such a lane is neither traced nor refilled until its chunk is swept
   int usub = 0;
@@ -274,12 +311,20 @@
     if (kLaneLds) {
       lane_ws[tid] = (uint32_t)w;
       lane_ws[kBlock + tid] = (uint32_t)(w >> 32);
+    } else if (kCarryLds) {
+      lds_u32 *q = carry_at(7, tid);
+      q[0] = (uint32_t)w;
+      q[kBlock] = (uint32_t)(w >> 32);
     } else {
       witem_r = w;
     }
   };
   auto witem = [&]() -> uint64_t {
     if (kLaneLds) return (uint64_t)lane_ws[tid] | ((uint64_t)lane_ws[kBlock + tid] << 32);
+    if (kCarryLds) {
+      const lds_u32 *q = carry_at(7, tid);
+      return (uint64_t)q[0] | ((uint64_t)q[kBlock] << 32);
+    }
     return witem_r;
   };
   auto set_ptri = [&](int t) {  // (read by the BVH instances' tree_skip only)
@@ -557,6 +602,10 @@
         bins_add(a.lds_edges != 0, edges, a.lds_edges ? bin * kEdgeL : bin * kEdgeW, 5, v);
       } else if (k == 0) {
         set_le(ke3(tri));
+        if (kTri0Carry) {
+          if (kCarryLds) *carry_at(6, tid) = (uint32_t)tri;
+          else tri0_r = tri;
+        }
       }
       nh = shading_normal(geom[tri], q);
       p = q;
@@ -772,7 +821,9 @@
             m[2] = M.z;
           }
         } else if (rslot == 0) {
-          Mlo = M;
+          // (kCarryLds: vertex 0 is at slot 0 and stores M = 1, so the resets of Mlo are not mirrored)
+          if (kCarryLds) carry_put3(3, M);
+          else Mlo = M;
         }
         rslot = (rslot + 1 == vcap_of()) ? 0 : rslot + 1;
       }
@@ -939,7 +990,23 @@
           const bool fst_o = is_badj<MODE>() || (valid && ((mk_ >> 14) & 1u));  // the chunk ends the path
           const int rr = valid ? KL - 1 - kk : 0;  // vertices after this one
           const V3 Lev = le();
-          const V3 LeL = mk(__shfl(Lev.x, ow), __shfl(Lev.y, ow), __shfl(Lev.z, ow));
+          V3 LeL = mk(__shfl(Lev.x, ow), __shfl(Lev.y, ow), __shfl(Lev.z, ow));
+          // the unbounded material adjoint: the owner's first triangle instead, and Le = Ke[tri_0]
+          // re-read through it (the same floats; the owner's three Le registers die in the trace loop)
+          if (kCarryLds) {  // the owners' carried words, written in this or an earlier iteration
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          }
+          // (taken only by the round's task lanes, whose owner has passed its vertex 0; a lane outside the
+          // round may never have written its word -- carry_ws is not initialised -- and the load below is
+          // unconditional; clamped as unsigned, like tk below, so nothing reaches global memory out of bounds)
+          int tri0c = 0;
+          if (kCarryLds) {
+            if (valid) tri0c = (int)min(*carry_at(6, (tid & ~63) + ow), (uint32_t)(nT - 1));
+          } else if (kTri0Carry) {
+            tri0c = (int)min((uint32_t)__shfl(tri0_r, ow), (uint32_t)(nT - 1));
+          }
+          if (kTri0Carry) LeL = ke3(tri0c);
           // this task's record (lanes past the round read vertex 0 of a valid column)
           uint32_t f0;
           float es, ck, sdv = 0.f, si = 0.f;
@@ -994,9 +1061,13 @@
                 Mk = mk(__shfl(m0.x, ow), __shfl(m0.y, ow), __shfl(m0.z, ow));
               }
             } else if (__ballot(owns && ulo > 0)) {
-              Mk = mk(__shfl(Mlo.x, ow), __shfl(Mlo.y, ow), __shfl(Mlo.z, ow));
+              if (kCarryLds) Mk = carry_get3(3, ow);
+              else Mk = mk(__shfl(Mlo.x, ow), __shfl(Mlo.y, ow), __shfl(Mlo.z, ow));
             }
-            if (__ballot(owns && !uend)) Sc = mk(__shfl(Scar.x, ow), __shfl(Scar.y, ow), __shfl(Scar.z, ow));
+            if (__ballot(owns && !uend)) {
+              if (kCarryLds) Sc = carry_get3(0, ow);
+              else Sc = mk(__shfl(Scar.x, ow), __shfl(Scar.y, ow), __shfl(Scar.z, ow));
+            }
           }
           // (the min()s keep a mis-indexed record from reaching global memory out of bounds)
           const int tk = min((int)(f0 & 0xffffu), nT - 1);
@@ -1090,8 +1161,9 @@
           // loads, issued as the sweep starts, finish under the chain)
           const float ax = __shfl(wx, ow), ay = __shfl(wy, ow), az = __shfl(wz, ow);
           // material adjoint: the path's first triangle (the stale Le is Ke[tri_0]),
-          // from the lane of the path's task 0 (every chunk starts at vertex 0)
-          const int tri0 = MATG ? __shfl(tk, lane - kk) : 0;
+          // from the lane of the path's task 0 (ADJ: every chunk starts at vertex 0);
+          // ADJU: from the owner lane, which carries it like Le (replay chunks start later)
+          const int tri0 = kTri0Carry ? tri0c : (MATG ? __shfl(tk, lane - kk) : 0);
           if (valid) {
             V3 dLd = Mk;
             if (esc && rr == 0) {  // the escape's stale re-add weights Ld by M_K = (M_K-1 T_K-1) c_K-1
@@ -1138,7 +1210,10 @@
             const V3 H = mk(A.x + B.x * S.x, A.y + B.y * S.y, A.z + B.z * S.z);
             const int sa = (owns ? st0 : lane) << 2;
             const V3 Hs = mk(bperm_f(sa, H.x), bperm_f(sa, H.y), bperm_f(sa, H.z));
-            if (owns) Scar = Hs;
+            if (owns) {
+              if (kCarryLds) carry_put3(0, Hs);
+              else Scar = Hs;
+            }
           }
           base = next;
         }

@@ -300,6 +300,19 @@ class Scene:
                                              g.ctypes.data_as(N.dp)), "adjoint_materials")
         return g[0], g[1], g[2]
 
+    def adjoint_materials_unbounded(self, adj, width, height, spp, seed=0, row_begin=0, row_end=None, row_step=1):
+        """``adjoint_materials`` for the reference's own estimator (no bounce
+        cap, paths end by Russian roulette or a miss): three (nT, 3) float64
+        arrays from one launch of the unbounded material adjoint
+        (ipt_adjoint_mat_unbounded_host).  The Kd block equals
+        ``adjoint(..., max_bounces=None)``; masks as in ``adjoint_materials``."""
+        p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
+        adj = np.ascontiguousarray(np.asarray(adj, np.float32).reshape(height, width, 3))
+        g = np.zeros((3, self.nT, 3), np.float64)
+        N.check(N.lib().ipt_adjoint_mat_unbounded_host(self.handle, C.byref(p), adj.ctypes.data_as(N.fp),
+                                                       g.ctypes.data_as(N.dp)), "adjoint_materials_unbounded")
+        return g[0], g[1], g[2]
+
     def adjoint_materials_batch(self, adj, kd, ks, ke, width, height, spp, max_bounces, seed=0, seed_stride=None,
                                 row_begin=0, row_end=None, row_step=1):
         """``adjoint_materials`` for S material sets in ONE batched launch

@@ -147,7 +147,8 @@ def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int
     load: ke rows outside ``scene.emitter_mask`` and ks rows outside
     ``scene.lobe_mask`` are ignored, and their gradients are exactly 0; the
     Phong exponent is not differentiated.  Refused (NativeError): the
-    unbounded estimator (max_bounces None) and batched inputs (S, nT, 3),
+    unbounded estimator (max_bounces None), which
+    ``render_materials_unbounded`` takes, and batched inputs (S, nT, 3),
     which ``render_materials_batch`` takes.
     `adjoint_seed` as in ``render``."""
     given = [t for t in (kd, ks, ke) if t is not None]
@@ -159,10 +160,56 @@ def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int
         if tuple(t.shape) != (scene.nT, 3):
             raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
     if max_bounces is None or max_bounces < 0:
-        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; "
-                            "give max_bounces in 0..62")
+        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported by "
+                            "render_materials; give max_bounces in 0..62 or call render_materials_unbounded")
     p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
     return _RenderMaterialsFn.apply(kd, ks, ke, scene, p, adjoint_seed)
+
+
+class _RenderMaterialsUnboundedFn(_RenderMaterialsFn):
+    """_RenderMaterialsFn at max_bounces = -1: the same forward
+    (ipt_render_mat_dev), the backward through ipt_adjoint_mat_unbounded_dev."""
+
+    @staticmethod
+    def backward(ctx, grad_hdr):
+        p = _replay_params(ctx.params, ctx.adjoint_seed)
+        kd, ks, ke = ctx.mat
+        adj = grad_hdr.float().contiguous()
+        g = torch.zeros((3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
+        if p.row_step > 1:  # interleaved rows: scatter into a full-frame image (as adjoint_band)
+            full = torch.zeros((p.height, p.width, 3), device=adj.device, dtype=torch.float32)
+            full[p.row_begin:p.row_end:p.row_step] = adj
+            base = full.data_ptr()
+        else:
+            base = adj.data_ptr() - p.row_begin * p.width * 3 * 4  # global-pixel indexing
+        N.check(N.lib().ipt_adjoint_mat_unbounded_dev(ctx.scene.handle, C.byref(p), _ptr(kd), _ptr(ks), _ptr(ke),
+                                                      base, g.data_ptr(), _stream(adj.device)),
+                "ipt_adjoint_mat_unbounded_dev")
+        out = [g[i].float() if (t is not None and ctx.needs_input_grad[i]) else None
+               for i, t in enumerate((kd, ks, ke))]
+        return out[0], out[1], out[2], None, None, None
+
+
+def render_materials_unbounded(scene: Scene, kd, ks, ke, width: int, height: int, spp: int, seed: int = 0,
+                               row_begin: int = 0, row_end=None, adjoint_seed=None, row_step: int = 1) -> torch.Tensor:
+    """``render_materials`` for the reference's own estimator (no bounce cap;
+    paths end by Russian roulette or a miss): the forward is
+    ipt_render_mat_dev with max_bounces = -1, the backward ONE launch of the
+    unbounded material adjoint (ipt_adjoint_mat_unbounded_dev: the ring and
+    replay sweep of ``render(max_bounces=None)``'s adjoint, emitting dL/dKd,
+    dL/dKs and dL/dKe).  kd, ks, ke, the masks, None and
+    no-grad inputs and `adjoint_seed` as in ``render_materials``; batched
+    (S, nT, 3) inputs are refused (NativeError)."""
+    given = [t for t in (kd, ks, ke) if t is not None]
+    if not given:
+        raise ValueError("render_materials_unbounded needs at least one of kd, ks, ke as a device tensor")
+    for t in given:
+        if t.dim() == 3:
+            raise N.NativeError("unbounded material adjoint: the scene batch (n_scenes > 1) is not supported")
+        if tuple(t.shape) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+    p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
+    return _RenderMaterialsUnboundedFn.apply(kd, ks, ke, scene, p, adjoint_seed)
 
 
 class _RenderMaterialsBatchFn(torch.autograd.Function):
@@ -213,8 +260,8 @@ def render_materials_batch(scene: Scene, kd, ks, ke, width: int, height: int, sp
             raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
                              [tuple(u.shape) for u in given])
     if max_bounces is None or max_bounces < 0:
-        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported; "
-                            "give max_bounces in 0..62")
+        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported by the "
+                            "scene batch; give max_bounces in 0..62 (one set: render_materials_unbounded)")
     stride = width * height * spp if seed_stride is None else int(seed_stride)
     p = N.make_params(width, height, spp, max_bounces, seed)
     return _RenderMaterialsBatchFn.apply(kd, ks, ke, scene, p, stride, adjoint_seed)

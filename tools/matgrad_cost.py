@@ -6,6 +6,11 @@ against the Kd-only bounded adjoint (ipt_adjoint_dev) on the same scenes:
 HIP events around each launch on one stream, the two kernels alternated so
 that clock and thermal drift hit both alike; medians and the ratio per scene
 (c3_phong: the SPEC instances; cornell: the diffuse ones).
+
+    python tools/matgrad_cost.py --unbounded > matgrad_cost_unbounded.json
+
+times the unbounded pair instead (max_bounces = -1): ipt_adjoint_mat_unbounded_dev
+against ipt_adjoint_dev.
 """
 import argparse
 import ctypes as C
@@ -40,15 +45,19 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--bounces", type=int, default=4)
+    ap.add_argument("--unbounded", action="store_true", help="the unbounded pair (max_bounces = -1)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     L = N.lib()
     stream = torch.cuda.current_stream().cuda_stream
-    out = {"size": a.size, "spp": a.spp, "max_bounces": a.bounces, "launches": a.launches, "warmup": a.warmup,
+    mb = None if a.unbounded else a.bounces
+    mat_name = "adjoint_mat_unbounded_dev" if a.unbounded else "adjoint_mat_dev"
+    mat_fn = L.ipt_adjoint_mat_unbounded_dev if a.unbounded else L.ipt_adjoint_mat_dev
+    out = {"size": a.size, "spp": a.spp, "max_bounces": -1 if a.unbounded else a.bounces, "launches": a.launches, "warmup": a.warmup,
            "timer": "HIP events per launch, kernels alternated on one stream", "scenes": {}}
     for name, objs in SCENES.items():
         S = Scene(objs)
-        p = N.make_params(a.size, a.size, a.spp, a.bounces, 0)
+        p = N.make_params(a.size, a.size, a.spp, mb, 0)
         adj = torch.rand((a.size, a.size, 3), device="cuda") + 0.5
         g1 = torch.zeros((S.nT, 3), device="cuda", dtype=torch.float64)
         g3 = torch.zeros((3, S.nT, 3), device="cuda", dtype=torch.float64)
@@ -57,12 +66,11 @@ def main():
             N.check(L.ipt_adjoint_dev(S.handle, C.byref(p), None, adj.data_ptr(), g1.data_ptr(), stream), "adjoint")
 
         def materials():
-            N.check(L.ipt_adjoint_mat_dev(S.handle, C.byref(p), None, None, None, adj.data_ptr(), g3.data_ptr(),
-                                          stream), "adjoint_mat")
+            N.check(mat_fn(S.handle, C.byref(p), None, None, None, adj.data_ptr(), g3.data_ptr(), stream), mat_name)
 
-        times = {"adjoint_dev": [], "adjoint_mat_dev": []}
+        times = {"adjoint_dev": [], mat_name: []}
         for i in range(a.warmup + a.launches):
-            for key, fn in (("adjoint_dev", kd_only), ("adjoint_mat_dev", materials)):
+            for key, fn in (("adjoint_dev", kd_only), (mat_name, materials)):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 fn()
@@ -78,9 +86,8 @@ def main():
             "nT": S.nT, "nE": S.nE,
             "adjoint_dev_ms": {"median": med["adjoint_dev"], "min": min(times["adjoint_dev"]),
                                "max": max(times["adjoint_dev"])},
-            "adjoint_mat_dev_ms": {"median": med["adjoint_mat_dev"], "min": min(times["adjoint_mat_dev"]),
-                                   "max": max(times["adjoint_mat_dev"])},
-            "ratio_of_medians": med["adjoint_mat_dev"] / med["adjoint_dev"],
+            mat_name + "_ms": {"median": med[mat_name], "min": min(times[mat_name]), "max": max(times[mat_name])},
+            "ratio_of_medians": med[mat_name] / med["adjoint_dev"],
             "kd_block_max_rel_diff": kd_rel, "launches": n,
         }
         S.close()
