@@ -1425,24 +1425,41 @@ __device__ __forceinline__ V3 shading_normal(const TriGeom &g, V3 q) {
 // org: the camera origin M * (0,0,0,1) = fma(M3, 1, fma(M2, 0, fma(M1, 0, M0 * 0)))
 // per row, the same for every ray: evaluated once on the host with these
 // operations (the launch arguments' cam_org) instead of per lane.
-__device__ __forceinline__ void camera_ray(const float *cam, const float *org, Rng &st, int r, int c, int W, int H,
-                                           float rcW, float rcH, V3 &p, V3 &d) {
-  const float u0 = uniform(st), u1 = uniform(st);
+// The pieces, for the in-phase refill of the fused forward (trace_body.h,
+// DESIGN.md §17), which runs the rotation and unit() once for camera rays and
+// sampled directions alike; camera_ray composes them operation for operation.
+// camera_local: the ray's direction in camera space from the two draws and
+// the pixel's column and row as floats ((float)c, (float)r).
+__device__ __forceinline__ V3 camera_local(float u0, float u1, float cf, float rf, int W, int H, float rcW, float rcH) {
   // (2(c+u0)) / W: numerator in [2^-32, 2W], W >= 1 -- in div_inrange's range.
   // d0 = (x, y, 1): x and y are 0 or multiples of 2^-24 (Sterbenz), n2 in
   // [1, 3] -- in unit_in_range's range.
-  const float nx = 2.f * ((float)c + u0), ny = 2.f * ((float)r + u1);
+  const float nx = 2.f * (cf + u0), ny = 2.f * (rf + u1);
   const float x = (rcW != 0.f ? nx * rcW : div_inrange(nx, (float)W)) - 1.f;
   const float y = 1.f - (rcH != 0.f ? ny * rcH : div_inrange(ny, (float)H));
-  const V3 d0 = unit_in_range(mk(x, y, 1.f));
-  float dr[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float *M = cam + 4 * i;
-    dr[i] = fmaf(M[3], 0.f, fmaf(M[2], d0.z, fmaf(M[1], d0.y, M[0] * d0.x)));
-  }
+  return unit_in_range(mk(x, y, 1.f));
+}
+// rotate3: rows R0, R1, R2 (three floats each) times h, sampleNextDir's and
+// Ray::transform's fma chain.
+__device__ __forceinline__ V3 rotate3(const float *R0, const float *R1, const float *R2, V3 h) {
+  return mk(fmaf(R0[2], h.z, fmaf(R0[1], h.y, R0[0] * h.x)), fmaf(R1[2], h.z, fmaf(R1[1], h.y, R1[0] * h.x)),
+            fmaf(R2[2], h.z, fmaf(R2[1], h.y, R2[0] * h.x)));
+}
+// camera_w0: Ray::transform's fourth term, the translation column times the
+// direction's w = 0 (a -0 sum becomes +0, every other value passes unchanged).
+__device__ __forceinline__ V3 camera_w0(const float *cam, V3 v) {
+  return mk(fmaf(cam[3], 0.f, v.x), fmaf(cam[7], 0.f, v.y), fmaf(cam[11], 0.f, v.z));
+}
+__device__ __forceinline__ void camera_ray_f(const float *cam, const float *org, Rng &st, float rf, float cf, int W, int H,
+                                             float rcW, float rcH, V3 &p, V3 &d) {
+  const float u0 = uniform(st), u1 = uniform(st);
+  const V3 d0 = camera_local(u0, u1, cf, rf, W, H, rcW, rcH);
   p = mk(org[0], org[1], org[2]);
-  d = unit(mk(dr[0], dr[1], dr[2]));
+  d = unit(camera_w0(cam, rotate3(cam, cam + 4, cam + 8, d0)));
+}
+__device__ __forceinline__ void camera_ray(const float *cam, const float *org, Rng &st, int r, int c, int W, int H,
+                                           float rcW, float rcH, V3 &p, V3 &d) {
+  camera_ray_f(cam, org, st, (float)r, (float)c, W, H, rcW, rcH, p, d);
 }
 
 // Phong lobe of BSDF (path_trace.cu:19-22)

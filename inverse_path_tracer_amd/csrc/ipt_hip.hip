@@ -498,6 +498,54 @@ __device__ __forceinline__ void item_ray(const TraceArgs &a, uint64_t seed, uint
   item_ray_ls(a, seed, lp, sj, st, p, d, r, c);
 }
 
+// The fused forward's brute-force instances (MODE_FWDM && !BVH) give a lane
+// whose path has just ended its next sample inside the shading phase, where
+// the continuing lanes sample their next direction: draws, rotation and
+// unit() then run once for both groups, and the refill at the loop top is
+// entered only at group boundaries.  With it the pixel part
+// of item_ray_ls is evaluated once per group of pixels, not per sample.
+// 0: the loop as before (make variant, A/B timing).
+#ifndef IPT_INPHASE_REFILL
+#define IPT_INPHASE_REFILL 1
+#endif
+#ifndef IPT_INPHASE_MERGE  // 0: only the per-group pixel entries, refill at the loop top as before (A/B timing)
+#define IPT_INPHASE_MERGE 1
+#endif
+#ifndef IPT_INPHASE_PACK  // 1: the waiting item packed into the item word in the diffuse instances too (A/B timing)
+#define IPT_INPHASE_PACK 0
+#endif
+template <int MODE, bool BVH>
+constexpr bool kInphase() {
+  return IPT_INPHASE_REFILL && MODE == MODE_FWDM && !BVH;
+}
+// Words per pixel of a group's entry table: seed + pixel * spp (lo, hi),
+// (float)c, (float)r -- item_ray_ls's pixel part; a sample adds its index s.
+constexpr int kEntryWords = 4;
+static inline uint32_t fused_entry_words(uint32_t group, bool bvh) {
+  return (IPT_INPHASE_REFILL && !bvh) ? kEntryWords * group : 0u;
+}
+__device__ __forceinline__ void pixel_entry(const TraceArgs &a, uint64_t seed, uint64_t lp, uint32_t e[kEntryWords]) {
+  int r, c;
+  local_rc(a, lp, r, c);
+  uint64_t g0;  // the pixel's first global sample index
+  if (a.idx32) {
+    const uint32_t pixel = (uint32_t)r * (uint32_t)a.W + (uint32_t)c;
+    g0 = (uint64_t)pixel * (uint32_t)a.spp;
+  } else {
+    g0 = ((uint64_t)r * (uint64_t)a.W + (uint64_t)c) * (uint64_t)a.spp;
+  }
+  g0 += seed;
+  e[0] = (uint32_t)g0;
+  e[1] = (uint32_t)(g0 >> 32);
+  e[2] = __float_as_uint((float)c);
+  e[3] = __float_as_uint((float)r);
+}
+// Timing-only ablations of the loop-top refill (images are wrong): 1 skips
+// the camera math, 2 the item math too
+#ifndef IPT_REFILL_ABLATE
+#define IPT_REFILL_ABLATE 0
+#endif
+
 // ---------------------------------------------------------------------------
 // Minimum resident 256-thread blocks per CU (= waves per SIMD) requested per
 // integrator; 0 lets the compiler choose.  Round 1 measured 6 best (80 VGPRs,
@@ -1058,7 +1106,14 @@ GpuScene *gpu_upload(const HostScene &host, std::string *err) {
   }
   std::vector<TriPair> pairs((host.isect.size() + 1) / 2);
   pack_pairs(host.isect.data(), (int)host.isect.size(), pairs.data());
-  if (upload(&s->isect, host.isect) || upload(&s->pairs, pairs) || upload(&s->geom, host.geom) || upload(&s->mat, host.mat) ||
+  // record nT of the device's TriGeom array: the camera's rotation as a
+  // sampling frame, gathered by the in-phase refill's lanes where a
+  // continuing lane gathers its triangle's R (trace_body.h)
+  std::vector<TriGeom> geom(host.geom);
+  geom.resize((size_t)host.nT + 1, TriGeom());
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) geom[(size_t)host.nT].R[i][j] = host.cam[4 * i + j];
+  if (upload(&s->isect, host.isect) || upload(&s->pairs, pairs) || upload(&s->geom, geom) || upload(&s->mat, host.mat) ||
       upload(&s->kd, host.kd) || upload(&s->emit_tri, host.emit_tri) || upload(&s->emit_cdf, host.emit_cdf) ||
       upload(&s->emit_pmf, host.emit_pmf) || upload(&s->emit_pmfr, pmf_reciprocals(host.emit_pmf)) ||
       upload(&s->big_pairs, host.bvh_big_pairs) || upload(&s->big_idx, host.bvh_big_idx) ||
@@ -1786,7 +1841,9 @@ static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, 
     a.group = (uint32_t)fs.group;
     a.chunk = (uint32_t)(fs.group * fs.per_grab);  // pixels per grab; launch_inst may halve it for thin launches
     a.nslots = fs.slots;
-    a.mean_wstride = (uint32_t)(((2 * fs.slots + 3) & ~3) + 3 * fs.slots * p.spp + 3) & ~3u;  // floats per wave
+    // floats per wave: slot table, the group's pixel entries (brute force), slots
+    a.mean_wstride = (uint32_t)(((2 * fs.slots + 3) & ~3) + fused_entry_words((uint32_t)fs.group, use_bvh(s)) +
+                                3 * fs.slots * p.spp + 3) & ~3u;
     a.ldr = ldr_dev;
     a.out_stride = (uint64_t)npix * 3;  // per material set: its own HDR (and LDR) image
     const size_t tail = (size_t)(kBlock / 64) * a.mean_wstride * sizeof(float);

@@ -348,11 +348,30 @@
   const int lane = tid & 63;
   // MODE_FWDM: this wave's slot table ([nslots] unfinished counts, [nslots]
   // pixels, padded to 16 B) and slots ([channel][sample] floats each)
+  // kInph (the in-phase refill): between the two, the current
+  // group's pixel entries (kEntryWords each, 16-B aligned, by place q in the group)
+  constexpr bool kInph = kInphase<MODE, BVH>();
+  constexpr bool kInphM = kInph && IPT_INPHASE_MERGE;  // 0: the entries only (A/B timing)
+  // kInphP: the sample taken in phase waits above the old path's item in the
+  // one item word; else in a register of its own.  The SPEC instances spill
+  // 16 B per lane with the register, the diffuse ones are 0.5% slower packed.
+  constexpr bool kInphP = kInphM && (SPEC || IPT_INPHASE_PACK);
   auto fused_tab = [&](const TraceArgs &A) -> lds_u32 * {
     return (lds_u32 *)(reinterpret_cast<char *>(lds) + A.mean_off) + (size_t)(tid >> 6) * A.mean_wstride;
   };
+  auto fused_entries = [&](const TraceArgs &A) -> lds_u32 * { return fused_tab(A) + ((2 * A.nslots + 3) & ~3); };
   auto fused_slots = [&](const TraceArgs &A) -> lds_f32 * {
-    return (lds_f32 *)(fused_tab(A) + ((2 * A.nslots + 3) & ~3));
+    return (lds_f32 *)(fused_tab(A) + ((2 * A.nslots + 3) & ~3) + (kInph ? kEntryWords * A.group : 0u));
+  };
+  // the sample s of the group's pixel q: seed, column and row from the pixel's
+  // entry -- item_ray_ls's values without its per-sample index arithmetic
+  auto entry_sample = [&](const TraceArgs &A, uint32_t q, uint32_t s, float &cf, float &rf) -> uint64_t {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) v4u lds_v4u;
+    const v4u e = *(const lds_v4u *)(fused_entries(A) + kEntryWords * q);
+    cf = __uint_as_float(e.z);
+    rf = __uint_as_float(e.w);
+    return (((uint64_t)e.y << 32) | (uint64_t)e.x) + (uint64_t)s;
   };
   // Sum the slots of `mask` (wave-uniform, <= 16 of them): lanes 3i + c take
   // the i-th slot's channel c and add v_s / spp over s = 0 .. spp-1 in sample
@@ -461,6 +480,17 @@
             const uint32_t sl = (gslots >> (4 * lane)) & 15u;
             tab[sl] = (uint32_t)a.spp;
             tab[a.nslots + sl] = glp + (uint32_t)lane;
+            if (kInph) {  // the pixel's entry, read by every sample of it that a lane takes
+              uint32_t e[kEntryWords];
+              pixel_entry(a, seed, glp + (uint32_t)lane, e);
+              lds_u32 *w = fused_entries(a) + kEntryWords * lane;
+#pragma unroll
+              for (int i = 0; i < kEntryWords; ++i) w[i] = e[i];
+            }
+          }
+          if (kInph) {  // the entries before the refills' reads (other lanes')
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
           }
         } else {
           exhausted = true;
@@ -499,10 +529,32 @@
           const uint32_t j = fj + rank;
           const uint32_t s = (gnp & (gnp - 1u)) == 0u ? j >> __builtin_ctz(gnp) : j / gnp;
           const uint32_t q = j - s * gnp;
-          int r, c;
-          item_ray_ls(a, seed, glp + q, s, st, p, d, r, c);
+          if (IPT_REFILL_ABLATE && !BVH) {  // timing only: no camera math (1), no item math either (2, 3)
+            uint64_t g = (uint64_t)(glp * (uint32_t)a.spp + j);
+            if (IPT_REFILL_ABLATE < 2) {
+              int r, c;
+              local_rc(a, glp + q, r, c);
+              g = (uint64_t)((uint32_t)r * (uint32_t)a.W + (uint32_t)c) * (uint32_t)a.spp + s;
+            }
+            rng_init(st, seed + g);
+            p = mk(a.cam_org[0], a.cam_org[1], a.cam_org[2]);
+            d = mk(a.cam[2], a.cam[6], a.cam[10]);  // the view axis: a unit vector into the scene
+            if (IPT_REFILL_ABLATE == 3) {  // the paths' statistics kept: the pixel's direction, neither rotated nor unit
+              const float u0 = uniform(st), u1 = uniform(st);
+              d = mk(2.f * ((float)((glp + q) & 511u) + u0) * a.rc_W - 1.f,
+                     1.f - 2.f * ((float)((glp + q) >> 9) + u1) * a.rc_H, 1.f);  // (a 512-wide frame)
+            }
+          } else if (kInph) {
+            float cf, rf;
+            rng_init(st, entry_sample(a, q, s, cf, rf));
+            camera_ray_f(a.cam, a.cam_org, st, rf, cf, a.W, a.H, a.rc_W, a.rc_H, p, d);
+          } else {
+            int r, c;
+            item_ray_ls(a, seed, glp + q, s, st, p, d, r, c);
+          }
           // the sample's LDS place: its pixel's slot, sample s
-          set_item((uint64_t)((gslots >> (4 * q)) & 15u) | ((uint64_t)s << 4));
+          if (kInph) set_item((uint64_t)(((gslots >> (4 * q)) & 15u) | (s << 4)));  // (one 32-bit value: s < 2^28)
+          else set_item((uint64_t)((gslots >> (4 * q)) & 15u) | ((uint64_t)s << 4));
           L = mk(0.f, 0.f, 0.f);
           set_le(L);
           Ld = L;
@@ -589,6 +641,10 @@
     const int tri = hit;
     V3 nh = p, din = d, sd = d, nd = d;
     bool shadow = false, cont = false;
+    // kInphM: the vertex passed Russian roulette; this lane's path ends here
+    // and it has taken its next sample, the item nitem (slot | s << 4)
+    bool wantc = false, refill = false;
+    uint32_t nitem = 0;
     int emitter = 0;
     float ct = 0.f, coeff = 0.f, speci = 0.f, specd = 0.f;
     if (vertex) {
@@ -631,7 +687,9 @@
       }
       if (!(a.max_bounces >= 0 && k == a.max_bounces)) {
         const float pr = uniform(st);  // Russian roulette, path_trace.cu:130-131
-        if (pr < kPRR) {                // sampleNextDir, path_trace.cu:91-109
+        if (kInphM) {                   // (the direction: below, merged with the refilling lanes' camera rays)
+          wantc = pr < kPRR;
+        } else if (pr < kPRR) {         // sampleNextDir, path_trace.cu:91-109
           const TriMat &m = mat[tri];
           const bool spec = SPEC && (MODE != MODE_GRAPH) && (m.flags & MAT_SPECULAR);
           const float uphi = uniform(st);
@@ -662,6 +720,74 @@
             if (SPEC && (m.flags & MAT_HAS_KS)) speci = phong(m.shininess, nh, din, nd);
             coeff = spec ? (dot3(nd, nh) / psamp) / kPRR : div_const<1>(div_const<0>(dot3(nd, nh)));  // psamp = kInvPiF
           }
+          cont = true;
+        }
+      }
+    }
+    if (kInphM) {
+      // In-phase refill.  A lane whose path ends in this
+      // iteration -- it missed, or its vertex does not continue -- takes the
+      // group's next sample here, handed out as at the loop top, and builds
+      // its camera ray in the block that samples the continuing lanes' next
+      // direction: two draws from the lane's state, a local vector under each
+      // group's own mask, then one rotation (the camera's is record nT of
+      // geom) and one unit() for both.  The old path's RNG state is dead by
+      // now: every draw of a vertex precedes this point.  L, Le, Ld, M, k and
+      // the work item still serve the old path to the end of the iteration;
+      // the lane is reset after its output write.
+      const bool ends = active && !wantc;
+      const uint64_t ask = __ballot(ends);
+      const uint32_t fn = gnp * (uint32_t)a.spp;
+      float ecf = 0.f, erf = 0.f;
+      if (ask && fj < fn) {  // wave-uniform
+        const uint32_t rank =
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(ask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ask, 0u));
+        if (ends && fj + rank < fn) {
+          const uint32_t j = fj + rank;
+          const uint32_t s = (gnp & (gnp - 1u)) == 0u ? j >> __builtin_ctz(gnp) : j / gnp;
+          const uint32_t q = j - s * gnp;
+          rng_init(st, entry_sample(a, q, s, ecf, erf));
+          nitem = ((gslots >> (4 * q)) & 15u) | (s << 4);
+          // kInphP: it waits (12 bits: slot, s < 256) above the old path's item, under a marker bit
+          if (kInphP) set_item(witem() | (uint64_t)((nitem | 0x1000u) << 16));
+          refill = true;
+        }
+        fj += (uint32_t)__popcll(ask);
+        fj = fj < fn ? fj : fn;
+      }
+      if (wantc || refill) {
+        const float ua = uniform(st);  // cont: phi's draw; refill: the camera's u0
+        const float ub = uniform(st);  // cont: theta's;    refill: u1
+        const TriMat &m = mat[refill ? 0 : tri];
+        const bool spec = SPEC && !refill && (m.flags & MAT_SPECULAR);
+        float psamp = kInvPiF;
+        V3 h;
+        if (refill) {
+          h = camera_local(ua, ub, ecf, erf, a.W, a.H, a.rc_W, a.rc_H);
+        } else {  // sampleNextDir, path_trace.cu:91-109
+          const float phi = (float)(2.0 * kPi * (double)ua);
+          float cth, sth;
+          if (!spec) {
+            cth = sqrt_core(ub);  // == (float)sqrt((double)ut) (innocuous double rounding); ut >= 2^-33
+            const float omu = 1.0f - ub;  // 0 or >= 2^-24
+            sth = omu > 0.f ? sqrt_core(omu) : 0.f;
+          } else {
+            const double cd = pow_d((double)ub, 1.0 / ((double)m.shininess + 1.0));
+            cth = (float)cd;
+            sth = (float)sqrt(1.0 - cd * cd);
+            psamp = pow_f((m.shininess + 1.f) * cth, m.shininess);
+          }
+          float sp, cp;
+          sincos_f(phi, sp, cp);
+          h = mk(sth * cp, sth * sp, cth);
+        }
+        const TriGeom &g = geom[refill ? nT : tri];
+        V3 v = rotate3(g.R[0], g.R[1], g.R[2], h);
+        if (refill) v = camera_w0(a.cam, v);  // Ray::transform's w term: these lanes only
+        nd = unit(v);
+        if (wantc) {
+          if (SPEC && (m.flags & MAT_HAS_KS)) speci = phong(m.shininess, nh, din, nd);
+          coeff = spec ? (dot3(nd, nh) / psamp) / kPRR : div_const<1>(div_const<0>(dot3(nd, nh)));  // psamp = kInvPiF
           cont = true;
         }
       }
@@ -869,7 +995,9 @@
       active = false;
       if (MODE == MODE_FWDM) {  // slot [channel][sample]
         const uint64_t wi = witem();
-        lds_f32 *o = fused_slots(a) + (uint32_t)(wi & 15u) * 3u * (uint32_t)a.spp + (uint32_t)(wi >> 4);
+        // (kInphP: the item is slot | s << 4 in 12 bits, the waiting one above it)
+        lds_f32 *o = fused_slots(a) + (uint32_t)(wi & 15u) * 3u * (uint32_t)a.spp +
+                     (kInphP ? ((uint32_t)wi >> 4) & 0xffu : (uint32_t)(wi >> 4));
         o[0] = L.x;
         o[a.spp] = L.y;
         o[2 * a.spp] = L.z;
@@ -917,6 +1045,18 @@
         comp &= comp - 1ull;
         sdone |= 1u << (__builtin_amdgcn_readlane((int)(witem() & 15u), l) & 31);
       }
+    }
+    // the old path is written and counted: a lane that took a sample in phase starts it
+    if (kInphM && (kInphP ? ((uint32_t)witem() >> 16) != 0u : refill)) {
+      L = mk(0.f, 0.f, 0.f);
+      set_le(L);
+      Ld = L;
+      M = mk(1.f, 1.f, 1.f);
+      k = 0;
+      p = mk(a.cam_org[0], a.cam_org[1], a.cam_org[2]);
+      d = nd;
+      set_item(kInphP ? (uint64_t)(((uint32_t)witem() >> 16) & 0xfffu) : (uint64_t)nitem);
+      active = true;
     }
     if (is_adj<MODE>()) {
       // Wave-parallel backward sweep (oracle adjoint_sample).  The vertices of
