@@ -283,6 +283,10 @@ typedef struct {
   v3 eo[3];   /* edge-plane normals (hoisted signedDistance, :497-503) */
   float ed[3];
   float R[3][3]; /* sampling frame (sampleNextDir, path_trace.cu:98-103) */
+  /* structure frozen at load: a Ks component != 0 in the
+   * MTL; that and a shininess != 0.  The integrator branches on these, never
+   * on the current values (oro_set_material_params may zero a row). */
+  int has_ks, specular;
 } otri_t;
 
 typedef struct {
@@ -1023,6 +1027,10 @@ static void camera_matrix(float M[4][4]) {
       M[i][j] = ((S[i][0] * V[j][0] + S[i][1] * V[j][1]) + S[i][2] * V[j][2]) + S[i][3] * V[j][3];
 }
 
+static int has_lobe(const omat_t *m) {
+  return m->specular[0] != 0.f || m->specular[1] != 0.f || m->specular[2] != 0.f;
+}
+
 void *oro_load_scene(int n, const float *poss, const float *oris, const float *scls,
                      const char **obj_files, const char **mtl_files) {
   oscene_t *sc = (oscene_t *)calloc(1, sizeof(oscene_t));
@@ -1051,6 +1059,8 @@ void *oro_load_scene(int n, const float *poss, const float *oris, const float *s
   for (int i = 0; i < sc->nT; i++) {
     otri_t *t = &sc->tris[i];
     t->idx = i;
+    t->has_ks = has_lobe(&t->m);
+    t->specular = t->has_ks && t->m.shininess != 0.f;
     if (t->m.emission[0] > 0.f || t->m.emission[1] > 0.f || t->m.emission[2] > 0.f) {
       t->idxE = ne++;
     }
@@ -1126,6 +1136,41 @@ void oro_set_materials(void *p, const float *in) {
   oscene_t *sc = (oscene_t *)p;
   for (int i = 0; i < sc->nT; i++)
     for (int j = 0; j < 3; j++) sc->tris[i].m.diffuse[j] = in[3 * i + j];
+}
+
+/* Per-triangle material VALUES, nT*3 floats each, each
+ * nullable.  Structure stays as loaded: the emitter list, cdf and pmf, has_ks
+ * and specular are untouched; Ks rows of lobe-less triangles and Ke rows of
+ * non-emitters are forced to 0. */
+void oro_set_material_params(void *p, const float *kd, const float *ks, const float *ke) {
+  oscene_t *sc = (oscene_t *)p;
+  for (int i = 0; i < sc->nT; i++) {
+    otri_t *t = &sc->tris[i];
+    for (int j = 0; j < 3; j++) {
+      if (kd) t->m.diffuse[j] = kd[3 * i + j];
+      if (ks) t->m.specular[j] = t->has_ks ? ks[3 * i + j] : 0.f;
+      if (ke) t->m.emission[j] = t->idxE >= 0 ? ke[3 * i + j] : 0.f;
+    }
+  }
+}
+void oro_get_material_params(void *p, float *kd, float *ks, float *ke) {
+  oscene_t *sc = (oscene_t *)p;
+  for (int i = 0; i < sc->nT; i++) {
+    const omat_t *m = &sc->tris[i].m;
+    for (int j = 0; j < 3; j++) {
+      if (kd) kd[3 * i + j] = m->diffuse[j];
+      if (ks) ks[3 * i + j] = m->specular[j];
+      if (ke) ke[3 * i + j] = m->emission[j];
+    }
+  }
+}
+/* nT ints each (nullable): the frozen lobe flag and the emitter index (-1: none) */
+void oro_material_structure(void *p, int *has_ks, int *idx_e) {
+  oscene_t *sc = (oscene_t *)p;
+  for (int i = 0; i < sc->nT; i++) {
+    if (has_ks) has_ks[i] = sc->tris[i].has_ks;
+    if (idx_e) idx_e[i] = sc->tris[i].idxE;
+  }
 }
 
 /* ------------------------------------------------------------------ */
@@ -1243,10 +1288,6 @@ static int pick_emitter(const oscene_t *sc, float u) {
   }
   return idx < sc->nE ? idx : sc->nE - 1;
 }
-static int is_specular(const omat_t *m) {
-  return (m->specular[0] != 0.f || m->specular[1] != 0.f || m->specular[2] != 0.f) &&
-         m->shininess != 0.f;
-}
 /* Phong lobe coefficient of BSDF (path_trace.cu:19-22) */
 static float phong_coeff(const omat_t *m, v3 nrm, v3 w, v3 wi) {
   float dn = dot3(nrm, wi);
@@ -1343,6 +1384,8 @@ static v3 sample_dir(const otri_t *tri, int spec, float shin, float *psamp, xorw
 typedef struct {
   int tri;
   float lo[3];     /* Ke * s (0 if NEE failed) */
+  float s;         /* the shadow ray's geometry term (0 if NEE failed) */
+  int et;          /* the sampled emitter's triangle (-1 if NEE failed) */
   float specd;     /* direct Phong coefficient (0 if none) */
   float coeff;     /* cos/p/p_RR (continued vertices) */
   float speci;     /* indirect Phong coefficient */
@@ -1378,11 +1421,11 @@ static void trace_forward(const oscene_t *sc, int W, int H, int spp, int max_bou
         for (int i = 0; i < 3; i++) Le[i] = tri->m.emission[i];
       v3 nh = get_normal(tri, q);
       nee_t ne = nee_geometry(sc, tri, q, nh, 1.f, &st, casts);
-      int spec = is_specular(&tri->m);
+      int spec = tri->specular;
       float specd = 0.f;
       if (ne.ok) {
         const otri_t *te = &sc->tris[ne.emitter];
-        if (tri->m.specular[0] != 0.f || tri->m.specular[1] != 0.f || tri->m.specular[2] != 0.f)
+        if (tri->has_ks)
           specd = phong_coeff(&tri->m, nh, ray.d, ne.toLight);
         for (int i = 0; i < 3; i++) {
           float lo = te->m.emission[i] * ne.s;
@@ -1397,6 +1440,8 @@ static void trace_forward(const oscene_t *sc, int W, int H, int spp, int max_bou
         vr->tri = h.tri;
         for (int i = 0; i < 3; i++)
           vr->lo[i] = ne.ok ? sc->tris[ne.emitter].m.emission[i] * ne.s : 0.f;
+        vr->s = ne.ok ? ne.s : 0.f;
+        vr->et = ne.ok ? ne.emitter : -1;
         vr->specd = specd;
         vr->coeff = 0.f;
         vr->speci = 0.f;
@@ -1408,7 +1453,7 @@ static void trace_forward(const oscene_t *sc, int W, int H, int spp, int max_bou
           float psamp;
           v3 nd = sample_dir(tri, spec, tri->m.shininess, &psamp, &st);
           float speci = 0.f;
-          if (tri->m.specular[0] != 0.f || tri->m.specular[1] != 0.f || tri->m.specular[2] != 0.f)
+          if (tri->has_ks)
             speci = phong_coeff(&tri->m, nh, ray.d, nd);
           float coeff = (dot3(nd, nh) / psamp) / P_RR;
           for (int i = 0; i < 3; i++) {
@@ -1645,9 +1690,13 @@ static void adj_buf_reserve(adj_buf_t *b, int n) {
   b->rec = (vrec_t *)realloc(b->rec, sizeof(vrec_t) * (size_t)b->cap);
   b->Mk = (float(*)[3])realloc(b->Mk, sizeof(float[3]) * (size_t)(b->cap + 1));
 }
+/* gks, gke (both or neither; nT*3 each) and st (ORO_MAT_STATS counters,
+ * nullable) belong to oro_adjoint_mat: DESIGN.md §13.2, the same fp32 products
+ * in the same order as the kernels' material block. */
+enum { ST_PATHS, ST_VERTS, ST_LONGEST, ST_ESCAPED, ST_SHADOW, ST_TRI0_EMIT, ST_KS_TERMS };
 static void adjoint_sample(const oscene_t *sc, int W, int H, int spp, int max_bounces,
                            uint64_t seed, int64_t gidx, const float *adj, double *grad,
-                           adj_buf_t *buf) {
+                           double *gks, double *gke, int64_t *st, adj_buf_t *buf) {
   float L[3];
   int K = 0, esc = 0;
   if (max_bounces < 0) { /* unbounded: length first */
@@ -1663,6 +1712,14 @@ static void adjoint_sample(const oscene_t *sc, int W, int H, int spp, int max_bo
   float a[3];
   for (int i = 0; i < 3; i++) a[i] = adj[pix * 3 + i] / (float)spp;
   const float *Le = sc->tris[rec[0].tri].m.emission;
+  const int tri0 = rec[0].tri, e0 = sc->tris[rec[0].tri].idxE >= 0;
+  if (st) {
+    st[ST_PATHS]++;
+    st[ST_VERTS] += K;
+    if (K > st[ST_LONGEST]) st[ST_LONGEST] = K;
+    st[ST_ESCAPED] += esc;
+    st[ST_TRI0_EMIT] += e0;
+  }
   float(*Mk)[3] = buf->Mk; /* prefix throughputs M_0..M_K */
   for (int i = 0; i < 3; i++) Mk[0][i] = 1.f;
   for (int k = 0; k < K; k++) {
@@ -1685,13 +1742,30 @@ static void adjoint_sample(const oscene_t *sc, int W, int H, int spp, int max_bo
   for (int k = K - 1; k >= 0; k--) {
     const omat_t *m = &sc->tris[rec[k].tri].m;
     int continued = (k < K - 1) || esc;
+    const int lobe = sc->tris[rec[k].tri].has_ks;
+    if (st) {
+      st[ST_SHADOW] += rec[k].s != 0.f;
+      st[ST_KS_TERMS] += lobe;
+    }
     for (int i = 0; i < 3; i++) {
       float dLd = Mk[k][i];
       if (esc && k == K - 1) dLd = dLd + Mk[K][i];
       float g = dLd * rec[k].lo[i];
+      const float dl = g;
       if (continued) g = g + ((rec[k].coeff / PI_F) * Mk[k][i]) * S[i];
       grad[(size_t)rec[k].tri * 3 + i] += (double)(a[i] * g);
       float Td = m->diffuse[i] + m->specular[i] * rec[k].specd;
+      if (gks) {
+        if (lobe) { /* (dLd lo) specd + ((c speci) M_k) S_k+1 */
+          float gs = dl * rec[k].specd;
+          if (continued) gs = gs + ((rec[k].coeff * rec[k].speci) * Mk[k][i]) * S[i];
+          gks[(size_t)rec[k].tri * 3 + i] += (double)(a[i] * gs);
+        }
+        if (rec[k].s != 0.f) /* (dLd D_k) s_k: the shadow ray found its emitter */
+          gke[(size_t)rec[k].et * 3 + i] += (double)(a[i] * ((dLd * Td) * rec[k].s));
+        if (e0) /* the stale first emission, re-added at every vertex */
+          gke[(size_t)tri0 * 3 + i] += (double)(a[i] * dLd);
+      }
       float Gk = Le[i] + Td * rec[k].lo[i];
       float Ti = m->diffuse[i] / PI_F + m->specular[i] * rec[k].speci;
       S[i] = Gk + (Ti * rec[k].coeff) * S[i];
@@ -1723,7 +1797,7 @@ int oro_adjoint(void *p, int W, int H, int spp, int max_bounces, uint64_t seed, 
     int64_t chunk = (n + nt - 1) / nt;
     int64_t lo = b + chunk * tid, hi = lo + chunk < e ? lo + chunk : e;
     for (int64_t g = lo; g < hi; g++)
-      adjoint_sample(sc, W, H, spp, max_bounces, seed, g, adj, gs + ng * (size_t)tid, &buf);
+      adjoint_sample(sc, W, H, spp, max_bounces, seed, g, adj, gs + ng * (size_t)tid, NULL, NULL, NULL, &buf);
     free(buf.rec);
     free(buf.Mk);
   }
@@ -1733,5 +1807,63 @@ int oro_adjoint(void *p, int W, int H, int spp, int max_bounces, uint64_t seed, 
     grad[i] = s;
   }
   free(gs);
+  return 0;
+}
+
+/* d(sum adj*I)/d(Kd, Ks, Ke): oro_adjoint's sample loop with the material
+ * terms of DESIGN.md §13.2.  Rows row_begin, row_begin + row_step, ... below
+ * row_end; with row_step 1 the samples are split over the threads exactly as
+ * in oro_adjoint, so the Kd block is its result bit for bit. */
+int oro_adjoint_mat(void *p, int W, int H, int spp, int max_bounces, uint64_t seed, int row_begin,
+                    int row_end, int row_step, const float *adj, double *grad, int64_t *stats) {
+  oscene_t *sc = (oscene_t *)p;
+  if (!sc || max_bounces > 62 || row_begin < 0 || row_end > H || row_begin > row_end || row_step < 1) {
+    set_err("bad adjoint arguments (max_bounces must be <= 62; < 0 = unbounded; row_step >= 1)");
+    return -1;
+  }
+  size_t nb = (size_t)sc->nT * 3, ng = 3 * nb;
+  int nth = nthreads();
+  double *gs = (double *)calloc(ng * (size_t)nth, sizeof(double));
+  int64_t *sts = (int64_t *)calloc((size_t)ORO_MAT_STATS * (size_t)nth, sizeof(int64_t));
+  const int64_t per_row = (int64_t)W * spp;
+  const int64_t nrows = (row_end - row_begin + row_step - 1) / row_step;
+  const int64_t n = nrows * per_row;
+#pragma omp parallel num_threads(nth)
+  {
+#ifdef _OPENMP
+    int tid = omp_get_thread_num();
+    int nt = omp_get_num_threads();
+#else
+    int tid = 0, nt = 1;
+#endif
+    adj_buf_t buf = {NULL, NULL, 0};
+    double *g = gs + ng * (size_t)tid;
+    int64_t chunk = (n + nt - 1) / nt;
+    int64_t lo = chunk * tid, hi = lo + chunk < n ? lo + chunk : n;
+    for (int64_t i = lo; i < hi; i++) {
+      int64_t gidx = ((int64_t)row_begin + (i / per_row) * row_step) * per_row + i % per_row;
+      adjoint_sample(sc, W, H, spp, max_bounces, seed, gidx, adj, g, g + nb, g + 2 * nb,
+                     sts + (size_t)ORO_MAT_STATS * (size_t)tid, &buf);
+    }
+    free(buf.rec);
+    free(buf.Mk);
+  }
+  for (size_t i = 0; i < ng; i++) {
+    double s = 0.0;
+    for (int t = 0; t < nth; t++) s += gs[ng * (size_t)t + i];
+    grad[i] = s;
+  }
+  if (stats) {
+    for (int j = 0; j < ORO_MAT_STATS; j++) {
+      int64_t v = 0;
+      for (int t = 0; t < nth; t++) {
+        int64_t x = sts[(size_t)ORO_MAT_STATS * (size_t)t + j];
+        v = j == ST_LONGEST ? (x > v ? x : v) : v + x;
+      }
+      stats[j] = v;
+    }
+  }
+  free(gs);
+  free(sts);
   return 0;
 }

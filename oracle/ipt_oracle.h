@@ -53,6 +53,16 @@ void oro_get_materials(void *scene, float *out);       /* nT*3 Kd */
 void oro_set_materials(void *scene, const float *in);  /* nT*3 Kd */
 void oro_camera_matrix(void *scene, float *out16);     /* row-major 4x4 */
 
+/* Per-triangle material VALUES, nT*3 floats each, each nullable (DESIGN.md
+ * §13.1).  Structure is frozen at load: which triangles carry a lobe (an MTL Ks
+ * component != 0) or are emitters, the emitter list, its cdf and pmf do not
+ * change, and the integrator branches on them, not on the values.  The setter
+ * forces Ks rows of lobe-less triangles and Ke rows of non-emitters to 0. */
+void oro_set_material_params(void *scene, const float *kd, const float *ks, const float *ke);
+void oro_get_material_params(void *scene, float *kd, float *ks, float *ke);
+/* nT ints each, nullable: the frozen lobe flag; the emitter index (-1: none). */
+void oro_material_structure(void *scene, int *has_ks, int *idx_e);
+
 /* Forward: per-sample radiance for global sample indices [s_begin,s_end)
  * (path_trace.cu:146-184).  out: (s_end-s_begin)*3 floats.  max_bounces<0
  * means unbounded (reference semantics).  casts (nullable) receives the
@@ -79,10 +89,29 @@ void oro_compress(int nT, const double *acc, float *data);
 
 /* Adjoint d(sum adj*I)/dKd of the forward estimator under common random
  * numbers (new capability).  adj: H*W*3, grad: nT*3
- * doubles.  Rows [row_begin,row_end) only.  Requires max_bounces >= 0. */
+ * doubles.  Rows [row_begin,row_end) only.  max_bounces < 0 is the unbounded
+ * estimator (each path is traced once for its length, then again with records);
+ * max_bounces > 62 is refused. */
 int oro_adjoint(void *scene, int W, int H, int spp, int max_bounces,
                 uint64_t seed, int row_begin, int row_end, const float *adj,
                 double *grad);
+
+/* Material adjoint d(sum adj*I)/d(Kd, Ks, Ke): oro_adjoint's
+ * sample loop with, per vertex k and channel, in fp32 and in this order,
+ *   Ks[tri_k]  (lobe triangles)      (dLd*lo)*specd  [+ ((c*speci)*M_k)*S_k+1]
+ *   Ke[et_k]   (s_k != 0)            (dLd*D_k)*s_k
+ *   Ke[tri_0]  (tri_0 an emitter)    dLd             at every vertex
+ * each times the pixel's adj/spp in fp32, then widened and summed in fp64.
+ * grad: 3*nT*3 doubles [Kd | Ks | Ke].  Rows row_begin, row_begin+row_step, ...
+ * below row_end.  The Kd block is oro_adjoint's bit for bit at row_step 1 and
+ * equal thread count.  stats (nullable): ORO_MAT_STATS counters -- paths with
+ * a vertex, vertices, longest path (vertices), escaped paths, vertices whose
+ * shadow ray found its emitter, paths whose first triangle is an emitter, Ks
+ * terms added (vertices on lobe triangles). */
+#define ORO_MAT_STATS 7
+int oro_adjoint_mat(void *scene, int W, int H, int spp, int max_bounces,
+                    uint64_t seed, int row_begin, int row_end, int row_step,
+                    const float *adj, double *grad, int64_t *stats);
 
 /* Closest hit (BVH::getIntersection over its single leaf, bvh.h:55-77 ->
  * Object::getIntersection, scene_basics.h:426-459) of n caller rays:

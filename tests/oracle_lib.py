@@ -15,6 +15,9 @@ LIB_PATH = os.path.join(ROOT, "oracle", "build", "libipt_oracle.so")
 FAST_LIB_PATH = os.path.join(ROOT, "oracle", "build", "libipt_oracle_fast.so")
 TRI_STRIDE = 57
 
+# the counters of oro_adjoint_mat, in its order
+MAT_STATS = ("paths", "vertices", "longest", "escaped", "shadow_found", "tri0_emitter", "ks_terms")
+
 _lib = None
 _libs = {}
 
@@ -59,6 +62,12 @@ def _bind(L):
                                   C.POINTER(C.c_int64)]
     L.oro_compress.argtypes = [C.c_int, dp, fp]
     L.oro_adjoint.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, fp, dp]
+    ip_ = C.POINTER(C.c_int)
+    L.oro_set_material_params.argtypes = [vp, fp, fp, fp]
+    L.oro_get_material_params.argtypes = [vp, fp, fp, fp]
+    L.oro_material_structure.argtypes = [vp, ip_, ip_]
+    L.oro_adjoint_mat.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int, fp, dp,
+                                  C.POINTER(i64)]
     L.oro_uniform_at.restype = C.c_float
     L.oro_uniform_at.argtypes = [C.c_uint64, C.c_int]
     L.oro_sincos.argtypes = [C.c_float, fp, fp]
@@ -174,6 +183,50 @@ class OracleScene:
             raise RuntimeError(self.L.oro_last_error().decode())
         return grad
 
+    # ---------------------------------------------------------- per-triangle materials
+    def material_params(self):
+        """(kd, ks, ke): the current per-triangle values, (nT, 3) float32 each."""
+        kd, ks, ke = (np.zeros((self.nT, 3), np.float32) for _ in range(3))
+        self.L.oro_get_material_params(self.ptr, _fp(kd), _fp(ks), _fp(ke))
+        return kd, ks, ke
+
+    def set_material_params(self, kd=None, ks=None, ke=None):
+        """Replace material VALUES (None: keep).  Structure is frozen at load: ks rows outside lobe_mask and
+        ke rows outside emitter_mask are forced to 0."""
+        arrs = [None if v is None else np.ascontiguousarray(np.asarray(v, np.float32).reshape(self.nT, 3))
+                for v in (kd, ks, ke)]
+        self.L.oro_set_material_params(self.ptr, *[None if a is None else _fp(a) for a in arrs])
+
+    def _structure(self):
+        has_ks, idx_e = np.zeros(self.nT, np.int32), np.zeros(self.nT, np.int32)
+        ip = C.POINTER(C.c_int)
+        self.L.oro_material_structure(self.ptr, has_ks.ctypes.data_as(ip), idx_e.ctypes.data_as(ip))
+        return has_ks != 0, idx_e >= 0
+
+    @property
+    def lobe_mask(self):
+        """bool (nT,): triangles whose MTL Ks had a non-zero component at load."""
+        return self._structure()[0]
+
+    @property
+    def emitter_mask(self):
+        """bool (nT,): triangles on the emitter list built at load."""
+        return self._structure()[1]
+
+    def adjoint_materials(self, W, H, spp, max_bounces, seed, adj, row_begin=0, row_end=None, row_step=1, stats=False):
+        """d(sum(adj * I))/d(Kd, Ks, Ke) as three (nT, 3) float64 arrays (max_bounces None: unbounded);
+        with stats=True also the oracle's counters as a dict."""
+        row_end = H if row_end is None else row_end
+        adj = np.ascontiguousarray(adj, np.float32).reshape(H, W, 3)
+        grad = np.zeros((3, self.nT, 3), np.float64)
+        st = np.zeros(len(MAT_STATS), np.int64)
+        rc = self.L.oro_adjoint_mat(self.ptr, W, H, spp, -1 if max_bounces is None else max_bounces, seed, row_begin,
+                                    row_end, row_step, _fp(adj), _dp(grad), st.ctypes.data_as(C.POINTER(C.c_int64)))
+        if rc:
+            raise RuntimeError(self.L.oro_last_error().decode())
+        if stats:
+            return grad[0], grad[1], grad[2], dict(zip(MAT_STATS, (int(x) for x in st)))
+        return grad[0], grad[1], grad[2]
 
     def closest_hit(self, origins, dirs):
         o = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(-1, 3))

@@ -3,8 +3,9 @@
 The material adjoint (trace_mat_kernel) returns
 d(sum adj*I)/d(Kd, Ks, Ke) of the bounded estimator under the forward's own
 paths.  With the paths fixed a sample's radiance is a polynomial in Kd and Ks
-and exactly linear and homogeneous in Ke, so the new blocks are checked
-without a new oracle:
+and exactly linear and homogeneous in Ke, so the new blocks are checked here
+by identities (tests/test_gpu_materials_oracle.py compares every entry with
+the oracle's material adjoint, which these identities pin on the CPU):
   * the forward with overrides is the oracle's, bit for bit;
   * the Kd block is the existing adjoint's (rtol 1e-9 against the oracle);
   * Ke: sum Ke * gKe equals the oracle's forward (homogeneity), per channel

@@ -3,8 +3,9 @@ paths end by Russian roulette or a miss (run with -m gpu).
 
 The unbounded material adjoint (trace_matu_kernel) is the
 unbounded adjoint's ring-and-replay sweep with the material adjoint's blocks.
-The oracle has no material adjoint, so -- as tests/test_gpu_materials.py does
-for the bounded one -- the new blocks are checked by identities:
+These tests predate the oracle's material adjoint (every entry is compared with
+it in tests/test_gpu_materials_oracle.py), so -- as tests/test_gpu_materials.py
+does for the bounded one -- the new blocks are checked by identities:
   * the Kd block is the oracle's unbounded adjoint (rtol 1e-9);
   * all three blocks equal the bounded material adjoint at a bounce cap that
     no path of the frame reaches, at the default ring and at rings
