@@ -276,6 +276,60 @@ int ipt_adjoint_mat_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, 
                               const float *kd_dev, const float *ks_dev, const float *ke_dev, const float *adj_dev,
                               double *grad_dev, void *stream);
 
+/* Views: caller-supplied cameras over one loaded scene.
+ * Every other entry point looks through the scene's own camera, the
+ * reference's constant Camera(CameraParams_t(true)); these render V cameras
+ * in one launch and sum ONE material gradient over them.  (Additive symbols:
+ * ipt_abi_version stays 5.)
+ *
+ * ipt_camera_look_at: the reference's camera matrix (scene.h:35-77) with its
+ * constants as arguments, in ipt_scene_camera's layout (16 floats, row
+ * major); eye 0, look +z, up +y, 90 degrees, aspect 1 gives ipt_scene_camera
+ * bit for bit.  As in the reference the eye lands in ROW 3, which rays never
+ * read: a ray starts at column 3 of rows 0..2 (out16[3], [7], [11]) and its
+ * direction is rows 0..2 times the camera-space direction -- to move a
+ * camera, write its position there.
+ *
+ * ipt_views_create validates n_views matrices once and uploads one device
+ * table (a host-only scene: validation only).  Refused with a message, *views
+ * = NULL: n_views outside 1..65535, a non-finite entry in rows 0..2, a 3x3
+ * part with zero determinant, an origin with a component beyond
+ * ipt_scene_camera_bound -- the acceleration structures are exact only for
+ * ray origins inside the coordinate bound fixed at load (scene extent and the
+ * scene's own camera); they are not rebuilt per view.  A
+ * handle belongs to its scene and is freed with ipt_views_free (before or
+ * after the scene); a NULL or freed handle is refused by every call. */
+int ipt_camera_look_at(const float eye[3], const float look[3], const float up[3], float fov_deg, float aspect,
+                       float *out16);
+int ipt_scene_camera_bound(void *scene, float *bound);
+int ipt_views_create(void *scene, int n_views, const float *cams /* n_views*16 */, void **views);
+void ipt_views_free(void *views);
+int ipt_views_count(void *views);
+/* One launch renders all V views with ONE material set (kd_dev / ks_dev /
+ * ke_dev: nT*3 device floats, NULL = the scene's own); view b uses seed
+ * p->seed + b*seed_stride and equals ipt_render_mat_dev through its camera
+ * bit for bit.  hdr_dev: V*rows*W*3.  max_bounces -1 or 0..62.
+ * ipt_adjoint_views_dev: d(sum_b sum adj_b*I_b)/d(Kd, Ks, Ke) -- adj_dev V
+ * full frames (V*H*W*3), grad_dev ONE block of 3*nT*3 doubles [Kd | Ks | Ke],
+ * ACCUMULATED over the views (zero it first).  Bounded estimator only
+ * (max_bounces 0..62); otherwise ipt_adjoint_mat_dev's refusals.  Every
+ * refusal happens before anything is enqueued. */
+int ipt_render_views_dev(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, const float *kd_dev,
+                         const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream);
+int ipt_adjoint_views_dev(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, const float *kd_dev,
+                          const float *ks_dev, const float *ke_dev, const float *adj_dev, double *grad_dev,
+                          void *stream);
+/* Host-memory forms with the scene's own materials (synchronous). */
+int ipt_render_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride,
+                          float *hdr /*V*rows*W*3*/);
+int ipt_adjoint_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride,
+                           const float *adj /*V*H*W*3*/, double *grad /*3*nT*3*/);
+/* Diagnostic: the camera rays of view `view` for n global sample indices
+ * (pixel * spp + sample, pixel row major, each in [0, W*H*spp)), from the
+ * trace kernels' own generator and camera code at seed p->seed. */
+int ipt_views_rays_host(void *scene, void *views, int view, const ipt_params_t *p, int64_t n,
+                        const int64_t *sample_index, float *org /* n*3 */, float *dir /* n*3 */);
+
 /* PNG helpers (RGB8). ipt_png_read with rgb == NULL only reports the size. */
 int ipt_png_write(const char *path, int width, int height, const uint8_t *rgb);
 int ipt_png_read(const char *path, int *width, int *height, uint8_t *rgb, int64_t capacity);

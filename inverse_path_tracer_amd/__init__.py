@@ -10,6 +10,7 @@ Submodules: ``ipt_cuda`` (the reference's FFI module, drop-in), ``scene``
 kernels), ``distributed`` (row-band / frame sharding over torch.distributed).
 """
 from ._native import NativeError, device_count  # noqa: F401
-from .scene import ObjectSpec, Scene, compress, parse_scene_text, png_read, png_write, unpack_graph  # noqa: F401
+from .scene import (ObjectSpec, Scene, Views, camera_at, camera_look_at, compress, parse_scene_text,  # noqa: F401
+                    png_read, png_write, unpack_graph)
 
 __version__ = "0.1.0"

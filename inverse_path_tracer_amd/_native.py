@@ -113,6 +113,16 @@ SIGNATURES = {
     "ipt_adjoint_mat_unbounded_host": (C.c_int, [vp, pp, fp, dp]),
     "ipt_render_mat_batch_dev": (C.c_int, [vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp]),
     "ipt_adjoint_mat_batch_dev": (C.c_int, [vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "ipt_camera_look_at": (C.c_int, [fp, fp, fp, C.c_float, C.c_float, fp]),
+    "ipt_scene_camera_bound": (C.c_int, [vp, fp]),
+    "ipt_views_create": (C.c_int, [vp, C.c_int, fp, C.POINTER(vp)]),
+    "ipt_views_free": (None, [vp]),
+    "ipt_views_count": (C.c_int, [vp]),
+    "ipt_render_views_dev": (C.c_int, [vp, vp, pp, C.c_uint64, vp, vp, vp, vp, vp]),
+    "ipt_adjoint_views_dev": (C.c_int, [vp, vp, pp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "ipt_render_views_host": (C.c_int, [vp, vp, pp, C.c_uint64, fp]),
+    "ipt_adjoint_views_host": (C.c_int, [vp, vp, pp, C.c_uint64, fp, dp]),
+    "ipt_views_rays_host": (C.c_int, [vp, vp, C.c_int, pp, C.c_int64, C.POINTER(C.c_int64), fp, fp]),
     "ipt_scene_set_accel": (C.c_int, [vp, C.c_int]),
     "ipt_scene_bvh_info": (C.c_int, [vp, C.POINTER(C.c_int32)]),
     "ipt_scene_export_bvh": (C.c_int, [vp, fp, fp, C.POINTER(C.c_int32)]),

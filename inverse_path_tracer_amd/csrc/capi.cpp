@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cstring>
 #include <ctime>
+#include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -553,6 +555,134 @@ int ipt_adjoint_mat_batch_dev(void *scene, const ipt_params_t *p, int n_scenes, 
   r.nscenes = n_scenes;
   r.seed_stride = seed_stride;
   return gpu_status(ipt::gpu_adjoint_mat_batch(s, r, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream));
+}
+
+// ---- views (caller-supplied cameras)
+int ipt_camera_look_at(const float eye[3], const float look[3], const float up[3], float fov_deg, float aspect,
+                       float *out16) {
+  if (!eye || !look || !up || !out16) {
+    fail("ipt_camera_look_at: bad arguments");
+    return -1;
+  }
+  ipt::camera_look_at(eye, look, up, fov_deg, aspect, out16);
+  return 0;
+}
+
+int ipt_scene_camera_bound(void *scene, float *bound) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !bound) {
+    if (s) fail("ipt_scene_camera_bound: bad arguments");
+    return -1;
+  }
+  *bound = ipt::gpu_camera_bound(s);
+  return 0;
+}
+
+// The live views handles: a NULL, freed or foreign pointer is refused with a
+// message instead of being dereferenced.
+static std::mutex g_views_mu;
+static std::set<void *> g_views;
+static ipt::GpuViews *as_views(void *views, const char *who) {
+  std::lock_guard<std::mutex> lk(g_views_mu);
+  if (!views || !g_views.count(views)) {
+    fail(std::string(who) + (views ? ": the views handle is not live (freed, or not from ipt_views_create)"
+                                   : ": null views handle"));
+    return nullptr;
+  }
+  return static_cast<ipt::GpuViews *>(views);
+}
+
+int ipt_views_create(void *scene, int n_views, const float *cams, void **views) {
+  if (views) *views = nullptr;
+  GpuScene *s = as_scene(scene);
+  if (!s || !views || !cams) {
+    if (s) fail("ipt_views_create: bad arguments (cams and views are required)");
+    return -1;
+  }
+  ipt::GpuViews *v = ipt::gpu_views_create(s, n_views, cams);
+  if (!v) return gpu_status(-1);
+  std::lock_guard<std::mutex> lk(g_views_mu);
+  g_views.insert(v);
+  *views = v;
+  return 0;
+}
+void ipt_views_free(void *views) {
+  {
+    std::lock_guard<std::mutex> lk(g_views_mu);
+    if (!views || !g_views.erase(views)) return;
+  }
+  ipt::gpu_views_free(static_cast<ipt::GpuViews *>(views));
+}
+int ipt_views_count(void *views) {
+  ipt::GpuViews *v = as_views(views, "ipt_views_count");
+  return v ? ipt::gpu_views_count(v) : -1;
+}
+
+static ipt::RenderParams views_params(const ipt_params_t *p, uint64_t seed_stride) {
+  ipt::RenderParams r = to_params(p);
+  r.seed_stride = seed_stride;
+  return r;
+}
+
+int ipt_render_views_dev(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, const float *kd_dev,
+                         const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_render_views_dev") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || !hdr_dev) {
+    fail("ipt_render_views_dev: bad arguments (params and hdr_dev are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_render_views(s, v, views_params(p, seed_stride), kd_dev, ks_dev, ke_dev, hdr_dev, stream));
+}
+
+int ipt_adjoint_views_dev(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, const float *kd_dev,
+                          const float *ks_dev, const float *ke_dev, const float *adj_dev, double *grad_dev,
+                          void *stream) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_adjoint_views_dev") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || !adj_dev || !grad_dev) {
+    fail("ipt_adjoint_views_dev: bad arguments (params, adj_dev and grad_dev are required)");
+    return -1;
+  }
+  return gpu_status(
+      ipt::gpu_adjoint_views(s, v, views_params(p, seed_stride), kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream));
+}
+
+int ipt_render_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, float *hdr) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_render_views_host") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || !hdr) {
+    fail("ipt_render_views_host: bad arguments (params and hdr are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_render_views_host(s, v, views_params(p, seed_stride), hdr));
+}
+
+int ipt_adjoint_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, const float *adj,
+                           double *grad) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_adjoint_views_host") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || !adj || !grad) {
+    fail("ipt_adjoint_views_host: bad arguments (params, adj and grad are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_adjoint_views_host(s, v, views_params(p, seed_stride), adj, grad));
+}
+
+int ipt_views_rays_host(void *scene, void *views, int view, const ipt_params_t *p, int64_t n,
+                        const int64_t *sample_index, float *org, float *dir) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_views_rays_host") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || n < 0 || (n > 0 && (!sample_index || !org || !dir))) {
+    fail("ipt_views_rays_host: bad arguments");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_views_rays_host(s, v, view, to_params(p), n, sample_index, org, dir));
 }
 
 int ipt_graph_dev(void *scene, const ipt_params_t *p, const uint8_t *target_dev, double *acc_dev, void *stream) {

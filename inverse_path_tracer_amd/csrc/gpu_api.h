@@ -65,6 +65,27 @@ int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev
 int gpu_adjoint_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
                           const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
 
+// Views: V caller-supplied cameras (ipt_scene_camera's layout, n*16 floats) over one scene, validated
+// once and uploaded as one device table (host-only scene: validated only).  nullptr + gpu_last_error()
+// when a view is refused.  gpu_camera_bound: the largest admissible |component| of a view's origin.
+struct GpuViews;
+GpuViews *gpu_views_create(GpuScene *s, int n, const float *cams);
+void gpu_views_free(GpuViews *v);
+int gpu_views_count(const GpuViews *v);
+float gpu_camera_bound(const GpuScene *s);
+// One launch over all views with ONE material set (kd / ks / ke nT*3, nullptr = the scene's own); view b
+// uses seed + b * p.seed_stride.  hdr_dev: V images; adj_dev: V full frames; grad_dev: ONE 3 x nT x 3
+// block [Kd | Ks | Ke], accumulated over the views.  The adjoint is bounded (max_bounces 0..62).
+int gpu_render_views(GpuScene *s, const GpuViews *v, RenderParams p, const float *kd_dev, const float *ks_dev,
+                     const float *ke_dev, float *hdr_dev, void *stream);
+int gpu_adjoint_views(GpuScene *s, const GpuViews *v, RenderParams p, const float *kd_dev, const float *ks_dev,
+                      const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
+int gpu_render_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, float *hdr);
+int gpu_adjoint_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, const float *adj, double *grad);
+// The camera rays of view `view` for n global sample indices (host arrays; diagnostic).
+int gpu_views_rays_host(GpuScene *s, const GpuViews *v, int view, RenderParams p, int64_t n, const int64_t *index,
+                        float *org, float *dir);
+
 // Host-memory conveniences (allocate, copy, run, copy back, synchronize).
 int gpu_render_samples_host(GpuScene *s, const RenderParams &p, float *samples);
 int gpu_render_host(GpuScene *s, const RenderParams &p, float *hdr, uint8_t *ldr);

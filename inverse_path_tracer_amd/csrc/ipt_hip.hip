@@ -435,6 +435,7 @@ __device__ __forceinline__ void local_rc(const TraceArgs &a, uint64_t lp, int &r
 #define IPT_CTR_STRIDE 32
 #endif
 constexpr int kCtrStride = IPT_CTR_STRIDE;
+constexpr int kViewFloats = 20;  // floats per entry of the views' table (trace_fwd_views_kernel)
 template <bool BVH>
 constexpr bool kGuided() {
   return BVH || IPT_BF_BIG > 1;
@@ -808,6 +809,7 @@ __global__ IPT_TRACE_BOUNDS void trace_kernel(
     const uint8_t *__restrict__ target, double *__restrict__ edges) {
   constexpr bool MATG = false;
   constexpr bool MATB = false;
+  constexpr bool VIEWS = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -828,6 +830,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_mat_kernel(
   static_assert(is_fwd<MODE>(), "forward instances only");
   constexpr bool MATG = false;
   constexpr bool MATB = true;
+  constexpr bool VIEWS = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -848,6 +851,7 @@ trace_mat_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const Tr
   constexpr int MODE = MODE_ADJ;
   constexpr bool MATG = true;
   constexpr bool MATB = false;
+  constexpr bool VIEWS = false;
 #include "trace_body.h"
 }
 
@@ -868,7 +872,67 @@ trace_matu_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const T
   constexpr int MODE = MODE_ADJU;
   constexpr bool MATG = true;
   constexpr bool MATB = false;
+  constexpr bool VIEWS = false;
 #include "trace_body.h"
+}
+
+// Views: the scene batch's grid split with the sets being V
+// cameras over ONE material set.  Set b renders with seed + b * seed_stride
+// into out + b * out_stride (the adjoint reads adj + b * H*W*3), but kd, mat,
+// kd/pi and the gradient carry no per-set offset, and the camera is entry b
+// of the views' table -- kViewFloats floats per view: the 16 of the matrix,
+// the origin's 3 (make_args' fmaf chain, evaluated at ipt_views_create), one
+// of padding (16-B entries).  The table is the TRAILING parameter: TraceArgs
+// and the leading parameters keep their kernarg offsets, and the shipped
+// instances their code.  __global__s of their own for the same reason.
+template <int MODE, bool SPEC, bool BVH>
+__global__ IPT_TRACE_BOUNDS void trace_fwd_views_kernel(
+    const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+    const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat, const float *__restrict__ kd,
+    const int *__restrict__ emit_tri, const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+    float *__restrict__ out_samples, const float *__restrict__ adj, double *__restrict__ grad,
+    const uint8_t *__restrict__ target, double *__restrict__ edges, const float *__restrict__ views) {
+  static_assert(is_fwd<MODE>(), "forward instances only");
+  constexpr bool MATG = false;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = true;
+  const int *const tri_emit = nullptr;
+#include "trace_body.h"
+}
+template <bool SPEC, bool BVH>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
+                          amdgpu_waves_per_eu(min_blocks<MODE_ADJ, BVH>()))) void
+trace_mat_views_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+                       const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat,
+                       const float *__restrict__ kd, const int *__restrict__ emit_tri,
+                       const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+                       float *__restrict__ out_samples, const float *__restrict__ adj, double *__restrict__ grad,
+                       const uint8_t *__restrict__ target, double *__restrict__ edges,
+                       const int *__restrict__ tri_emit, const float *__restrict__ views) {
+  constexpr int MODE = MODE_ADJ;
+  constexpr bool MATG = true;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = true;
+#include "trace_body.h"
+}
+
+// The diagnostic of ipt_views_rays_host: the megakernel's own rng_init and
+// camera_ray for caller-chosen global sample indices g (pixel = g / spp, row
+// major) of view `view`, written out as rays.
+__global__ __launch_bounds__(kBlock) void view_rays_kernel(const float *__restrict__ views, int view, int W, int H,
+                                                           int spp, float rcW, float rcH, uint64_t seed, int64_t n,
+                                                           const int64_t *__restrict__ index,
+                                                           float *__restrict__ org, float *__restrict__ dir) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t g = (uint64_t)index[i], pixel = g / (uint64_t)spp;
+  const float *cam = views + (size_t)view * kViewFloats;
+  Rng st;
+  rng_init(st, seed + g);
+  V3 p, d;
+  camera_ray(cam, cam + 16, st, (int)(pixel / (uint64_t)W), (int)(pixel % (uint64_t)W), W, H, rcW, rcH, p, d);
+  org[3 * i] = p.x, org[3 * i + 1] = p.y, org[3 * i + 2] = p.z;
+  dir[3 * i] = d.x, dir[3 * i + 1] = d.y, dir[3 * i + 2] = d.z;
 }
 
 // Per-launch TriMat tables of the material overrides (stream scratch): the
@@ -1029,13 +1093,14 @@ struct GpuScene {
   int *grad_map = nullptr, *slot_tri = nullptr;  // ADJ hot-set LDS slots (large scenes)
   int *tri_emit = nullptr;  // triangle -> emitter index or -1 (material overrides and adjoint)
   // slots 0..23: trace_kernel<mode, spec, bvh>; 24..27: trace_mat_kernel<spec, bvh>;
-  // 28..35: trace_fwd_mat_kernel<FWD | FWDM, spec, bvh>; 36..39: trace_matu_kernel<spec, bvh> (inst_slot)
-  int grid[40] = {0};       // resident workgroups per instance (0 = not queried)
-  size_t grid_lds[40] = {0};
-  size_t pick_base[40] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
-  size_t pick_tail[40] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
-  int pick_opt[40] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  // 28..35: trace_fwd_mat_kernel<FWD | FWDM, spec, bvh>; 36..39: trace_matu_kernel<spec, bvh>;
+  // 40..47: trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh> (inst_slot)
+  int grid[52] = {0};       // resident workgroups per instance (0 = not queried)
+  size_t grid_lds[52] = {0};
+  size_t pick_base[52] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
+  size_t pick_tail[52] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
+  int pick_opt[52] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
+                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   // dynamic-chunk counters per stream (stream_counters): `words` grab words,
   // zeroed once; every launch leaves them zero (TraceArgs::chunk_ctr)
   struct Counters {
@@ -1252,7 +1317,20 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 // adjoint (MODE_ADJ: trace_mat_kernel<SPEC, BVH>, MODE_ADJU: the unbounded
 // trace_matu_kernel<SPEC, BVH>), or (the forwards only) the batch forward with
 // per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
-enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2 };
+// KIND_VFWD / KIND_VMAT: the views' forward and bounded material adjoint
+// (trace_fwd_views_kernel, trace_mat_views_kernel).
+enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4 };
+constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }
+// The kernel of (MODE, SPEC, BVH, KIND), for the occupancy queries.
+template <int MODE, bool SPEC, bool BVH, int KIND>
+constexpr auto views_kernel() {
+  if constexpr (KIND == KIND_VMAT) {
+    static_assert(MODE == MODE_ADJ, "the views' adjoint is the bounded material adjoint");
+    return &trace_mat_views_kernel<SPEC, BVH>;
+  } else {
+    return &trace_fwd_views_kernel<MODE, SPEC, BVH>;
+  }
+}
 // The material adjoint's kernel for MODE (KIND_MATG).
 template <int MODE, bool SPEC, bool BVH>
 constexpr auto matg_kernel() {
@@ -1265,6 +1343,8 @@ template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr int inst_slot() {
   return (KIND == KIND_MATG   ? (MODE == MODE_ADJU ? 36 : 24)
           : KIND == KIND_FWDB ? 28 + (MODE == MODE_FWDM ? 4 : 0)
+          : KIND == KIND_VFWD ? 40 + (MODE == MODE_FWDM ? 4 : 0)
+          : KIND == KIND_VMAT ? 48
                               : MODE * 4) +
          (SPEC ? 2 : 0) + (BVH ? 1 : 0);
 }
@@ -1273,7 +1353,10 @@ static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
   const int slot = inst_slot<MODE, SPEC, BVH, KIND>();
   if (s->grid[slot] == 0 || s->grid_lds[slot] != lds_bytes) {
     int per_cu = 0, cus = 0;
-    if constexpr (KIND == KIND_MATG) {
+    if constexpr (kind_views(KIND)) {
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, views_kernel<MODE, SPEC, BVH, KIND>(), kBlock,
+                                                           lds_bytes));
+    } else if constexpr (KIND == KIND_MATG) {
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, matg_kernel<MODE, SPEC, BVH>(), kBlock, lds_bytes));
     } else if constexpr (KIND == KIND_FWDB) {
       HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, BVH>, kBlock,
@@ -1291,7 +1374,9 @@ static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
     s->grid_lds[slot] = lds_bytes;
     if (IPT_DEBUG_GRID)  // (make variant DEFS=-DIPT_DEBUG_GRID=1)
       std::fprintf(stderr, "[ipt] %s<%d,%d,%d>: %zu B LDS/block, %d blocks/CU x %d CUs\n",
-                   KIND == KIND_MATG   ? (MODE == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
+                   KIND == KIND_VFWD   ? "trace_fwd_views_kernel"
+                   : KIND == KIND_VMAT ? "trace_mat_views_kernel"
+                   : KIND == KIND_MATG ? (MODE == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
                    : KIND == KIND_FWDB ? "trace_fwd_mat_kernel"
                                        : "trace_kernel",
                    MODE, (int)SPEC, (int)BVH, lds_bytes, per_cu, cus);
@@ -1534,7 +1619,7 @@ static uint32_t launch_grabs(bool guided, uint64_t units, uint64_t c, uint64_t s
 template <int MODE, bool SPEC, bool BVH, int KIND = KIND_TRACE>
 static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float *kd_dev, float *out, const float *adj,
                        double *grad, const uint8_t *target, double *edges, hipStream_t st,
-                       const TriMat *mat_dev = nullptr) {
+                       const TriMat *mat_dev = nullptr, const float *views_dev = nullptr) {
   int grid = 0;
   if (lds > 160 * 1024) {
     gpu_set_error("LDS footprint of the launch exceeds 160 KiB");
@@ -1607,7 +1692,15 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float 
     return -1;
   }
   const TriMat *mat = mat_dev ? mat_dev : s->mat;
-  if constexpr (KIND == KIND_MATG)
+  if constexpr (KIND == KIND_VMAT)
+    hipLaunchKernelGGL((trace_mat_views_kernel<SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs,
+                       s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad,
+                       target, edges, s->tri_emit, views_dev);
+  else if constexpr (KIND == KIND_VFWD)
+    hipLaunchKernelGGL((trace_fwd_views_kernel<MODE, SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect,
+                       s->pairs, s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out,
+                       adj, grad, target, edges, views_dev);
+  else if constexpr (KIND == KIND_MATG)
     hipLaunchKernelGGL((matg_kernel<MODE, SPEC, BVH>()), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs, s->geom,
                        mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad, target,
                        edges, s->tri_emit);
@@ -1652,7 +1745,9 @@ static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) 
       const size_t l = bvh_lds_offset(bvh_lds(s, b, base, opt[k][0], opt[k][1], is_fwd<MODE>())) + tail;
       if (l > 160 * 1024) continue;
       int per_cu = 0;
-      if constexpr (KIND == KIND_MATG) {
+      if constexpr (kind_views(KIND)) {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, views_kernel<MODE, SPEC, true, KIND>(), kBlock, l));
+      } else if constexpr (KIND == KIND_MATG) {
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, matg_kernel<MODE, SPEC, true>(), kBlock, l));
       } else if constexpr (KIND == KIND_FWDB) {
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, true>, kBlock, l));
@@ -1682,17 +1777,18 @@ static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) 
 template <int MODE, int KIND = KIND_TRACE>
 static int launch(GpuScene *s, TraceArgs a, size_t lds, const float *kd_dev, float *out, const float *adj,
                   double *grad, const uint8_t *target, double *edges, hipStream_t st, size_t tail = 0,
-                  const TriMat *mat_dev = nullptr) {
+                  const TriMat *mat_dev = nullptr, const float *views_dev = nullptr) {
   // a batch's per-launch table holds one TriMat table per set (pack_materials);
   // its forward runs the instances that offset mat per set
-  a.mat_stride = (mat_dev && a.nscenes > 1) ? (uint32_t)a.nT : 0u;
+  // (views: one table, one kd for every set)
+  a.mat_stride = (mat_dev && a.nscenes > 1 && !kind_views(KIND)) ? (uint32_t)a.nT : 0u;
   if constexpr (is_fwd<MODE>() && KIND == KIND_TRACE) {
     if (a.mat_stride)
       return launch<MODE, KIND_FWDB>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, tail, mat_dev);
   }
   StreamScratch kdpi;
   if (MODE != MODE_GRAPH && !a.kd_tables && a.n_samples > 0) {
-    const int n = 3 * s->host.nT * a.nscenes;
+    const int n = 3 * s->host.nT * (kind_views(KIND) ? 1 : a.nscenes);
     if (kdpi.alloc((size_t)n * sizeof(float), st)) return -1;
     hipLaunchKernelGGL(kdpi_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, kd_dev ? kd_dev : s->kd, n,
                        (float *)kdpi.p);
@@ -1712,16 +1808,16 @@ static int launch(GpuScene *s, TraceArgs a, size_t lds, const float *kd_dev, flo
     if (s->has_ks) {
       if (launch_bvh_pick<MODE, true, KIND>(s, a, &lds, tail)) return -1;
       add_tail();
-      return launch_inst<MODE, true, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+      return launch_inst<MODE, true, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
     }
     if (launch_bvh_pick<MODE, false, KIND>(s, a, &lds, tail)) return -1;
     add_tail();
-    return launch_inst<MODE, false, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+    return launch_inst<MODE, false, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
   } else {
     add_tail();
     if (s->has_ks)
-      return launch_inst<MODE, true, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
-    return launch_inst<MODE, false, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev);
+      return launch_inst<MODE, true, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
+    return launch_inst<MODE, false, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
   }
 }
 
@@ -1741,13 +1837,14 @@ int gpu_pixel_mean(const float *samples_dev, int64_t npix, int spp, float *hdr_d
   return 0;
 }
 
+template <int KIND = KIND_TRACE>
 static int render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev,
-                             void *stream, const TriMat *mat_dev) {
+                             void *stream, const TriMat *mat_dev, const float *views_dev = nullptr) {
   if (check_params(s, p)) return -1;
   TraceArgs a = make_args(s, p);
   a.sample_major = 1;
-  return launch<MODE_FWD>(s, a, table_bytes(a), kd_dev, samples_dev, nullptr, nullptr, nullptr, nullptr,
-                          (hipStream_t)stream, 0, mat_dev);
+  return launch<MODE_FWD, KIND>(s, a, table_bytes(a), kd_dev, samples_dev, nullptr, nullptr, nullptr, nullptr,
+                                (hipStream_t)stream, 0, mat_dev, views_dev);
 }
 int gpu_render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev,
                           void *stream) {
@@ -1828,8 +1925,10 @@ static FusedShape fused_shape(const RenderParams &p, bool bvh) {
 }
 
 // mat_dev: the launch's TriMat table (nullptr: the scene's own)
+// KIND_VFWD: the sets are the views of views_dev (gpu_render_views)
+template <int KIND = KIND_TRACE>
 static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, float *hdr_dev, uint8_t *ldr_dev,
-                       void *stream, const TriMat *mat_dev) {
+                       void *stream, const TriMat *mat_dev, const float *views_dev = nullptr) {
   if (check_params(s, p)) return -1;
   const int64_t npix = (int64_t)band_rows(p) * p.width;
   const int sets = p.nscenes > 1 ? p.nscenes : 1;
@@ -1847,12 +1946,12 @@ static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, 
     a.ldr = ldr_dev;
     a.out_stride = (uint64_t)npix * 3;  // per material set: its own HDR (and LDR) image
     const size_t tail = (size_t)(kBlock / 64) * a.mean_wstride * sizeof(float);
-    return launch<MODE_FWDM>(s, a, table_bytes(a), kd_dev, hdr_dev, nullptr, nullptr, nullptr, nullptr,
-                             (hipStream_t)stream, tail, mat_dev);
+    return launch<MODE_FWDM, KIND>(s, a, table_bytes(a), kd_dev, hdr_dev, nullptr, nullptr, nullptr, nullptr,
+                                   (hipStream_t)stream, tail, mat_dev, views_dev);
   }
   StreamScratch ws;
   if (ws.alloc((size_t)sets * npix * p.spp * 3 * sizeof(float), (hipStream_t)stream)) return -1;
-  if (render_samples_sm(s, p, kd_dev, (float *)ws.p, stream, mat_dev)) return -1;
+  if (render_samples_sm<KIND>(s, p, kd_dev, (float *)ws.p, stream, mat_dev, views_dev)) return -1;
   return pixel_mean_sm_sets((const float *)ws.p, npix, p.spp, sets, hdr_dev, ldr_dev, stream);
 }
 int gpu_render(GpuScene *s, const RenderParams &p, const float *kd_dev, float *hdr_dev, uint8_t *ldr_dev,
@@ -1963,7 +2062,8 @@ int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev
 // dL/dKd, dL/dKs, dL/dKe in one launch of trace_mat_kernel (the bounded
 // adjoint only); grad_dev: 3 x nT x 3 doubles [Kd | Ks | Ke], accumulated.
 static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
-                            const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
+                            const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream,
+                            const float *views_dev = nullptr);
 int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
                     const float *adj_dev, double *grad_dev, void *stream) {
   if (check_params(s, p)) return -1;
@@ -1983,8 +2083,10 @@ int gpu_adjoint_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_de
   return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream);
 }
 
+// views_dev: the sets are views over ONE material set and one gradient (gpu_adjoint_views)
 static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
-                            const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+                            const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream,
+                            const float *views_dev) {
   if (p.max_bounces < 0) {
     gpu_set_error("material adjoint: the unbounded estimator (max_bounces < 0) is not supported here; give max_bounces in 0..62, or call ipt_adjoint_mat_unbounded_dev (one material set)");
     return -1;
@@ -2014,13 +2116,171 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
     gpu_set_error("material adjoint: LDS footprint (Kd/Ks/Ke bins + tables + vertex records) exceeds 160 KiB; lower max_bounces");
     return -1;
   }
-  const int sets = p.nscenes > 1 ? p.nscenes : 1;
+  const int sets = (p.nscenes > 1 && !views_dev) ? p.nscenes : 1;
   StreamScratch tab, kdrep;
   const TriMat *mat = nullptr;
   if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
   if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
+  if (views_dev)
+    return launch<MODE_ADJ, KIND_VMAT>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr,
+                                       (hipStream_t)stream, 0, mat, views_dev);
   return launch<MODE_ADJ, KIND_MATG>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream, 0,
                                 mat);
+}
+
+// ------------------------------------------------------------ views
+// camera_ray's origin M * (0,0,0,1) per row, with its own operations (fmaf is
+// the IEEE fma on host and device); make_args evaluates the same chain for
+// the scene's camera.
+static void camera_origin(const float *cam, float *org) {
+  for (int i = 0; i < 3; ++i) {
+    const float *M = cam + 4 * i;
+    org[i] = std::fmaf(M[3], 1.f, std::fmaf(M[2], 0.f, std::fmaf(M[1], 0.f, M[0] * 0.f)));
+  }
+}
+
+struct GpuViews {
+  GpuScene *scene = nullptr;
+  int n = 0;
+  std::vector<float> tab;  // n x kViewFloats: matrix, origin, padding
+  float *dev = nullptr;    // the same on the device (nullptr: host-only scene)
+};
+
+float gpu_camera_bound(const GpuScene *s) { return (float)(scene_coord_bound(s->host) - 1.0); }
+
+// Validated once, here: the launches take the table as it is.  The origin
+// bound is the one the acceptance boxes, the pair culls and the plane margin
+// were built for (bvh.cpp scene_coord_bound): they are exact
+// for ray origins with |coordinate| + 1 <= R only.
+GpuViews *gpu_views_create(GpuScene *s, int n, const float *cams) {
+  if (n < 1 || n > 65535) {
+    gpu_set_error("ipt_views_create: n_views must be in 1..65535");
+    return nullptr;
+  }
+  const double R = scene_coord_bound(s->host);
+  GpuViews *v = new GpuViews;
+  v->scene = s;
+  v->n = n;
+  v->tab.assign((size_t)n * kViewFloats, 0.f);
+  for (int b = 0; b < n; ++b) {
+    const float *M = cams + 16 * (size_t)b;
+    float *e = v->tab.data() + (size_t)b * kViewFloats;
+    std::string why;
+    for (int i = 0; i < 12 && why.empty(); ++i)
+      if (!std::isfinite(M[i])) why = "a non-finite entry in rows 0..2";
+    if (why.empty()) {
+      const double det = (double)M[0] * ((double)M[5] * M[10] - (double)M[6] * M[9]) -
+                         (double)M[1] * ((double)M[4] * M[10] - (double)M[6] * M[8]) +
+                         (double)M[2] * ((double)M[4] * M[9] - (double)M[5] * M[8]);
+      if (!(det != 0.0) || !std::isfinite(det)) why = "a 3x3 part with zero determinant";
+    }
+    std::memcpy(e, M, 16 * sizeof(float));
+    camera_origin(M, e + 16);
+    for (int i = 0; i < 3 && why.empty(); ++i)
+      if (!(std::fabs((double)e[16 + i]) + 1.0 <= R))
+        why = "its origin lies outside the bound the acceleration structures were built for (|component| <= " +
+              std::to_string(R - 1.0) + ", ipt_scene_camera_bound)";
+    if (!why.empty()) {
+      gpu_set_error("ipt_views_create: view " + std::to_string(b) + " has " + why);
+      delete v;
+      return nullptr;
+    }
+  }
+  if (s->on_device) {
+    const size_t bytes = v->tab.size() * sizeof(float);
+    if (hipMalloc(reinterpret_cast<void **>(&v->dev), bytes) != hipSuccess ||
+        hipMemcpy(v->dev, v->tab.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      gpu_set_error("ipt_views_create: the views' table could not be uploaded");
+      if (v->dev) (void)hipFree(v->dev);
+      delete v;
+      return nullptr;
+    }
+  }
+  return v;
+}
+void gpu_views_free(GpuViews *v) {
+  if (!v) return;
+  if (v->dev) (void)hipFree(v->dev);
+  delete v;
+}
+int gpu_views_count(const GpuViews *v) { return v->n; }
+
+// p.seed_stride is the caller's; the views are the launch's sets.
+static int views_params(GpuScene *s, const GpuViews *v, RenderParams &p) {
+  if (v->scene != s) {
+    gpu_set_error("views: the handle was created for another scene");
+    return -1;
+  }
+  p.nscenes = v->n;
+  return check_params(s, p);
+}
+
+// One launch renders every view with ONE material set (kd / ks / ke: nT*3
+// device arrays, nullptr = the scene's own); hdr_dev: V images.  View b is
+// gpu_render_mat of its camera at seed + b * seed_stride, bit for bit.
+int gpu_render_views(GpuScene *s, const GpuViews *v, RenderParams p, const float *kd_dev, const float *ks_dev,
+                     const float *ke_dev, float *hdr_dev, void *stream) {
+  if (views_params(s, v, p)) return -1;
+  if (p.max_bounces > kMaxAdjBounces) {
+    gpu_set_error("views: give max_bounces in 0..62, or -1 for the unbounded estimator");
+    return -1;
+  }
+  StreamScratch tab;
+  const TriMat *mat = nullptr;
+  if (pack_materials(s, ks_dev, ke_dev, 1, (hipStream_t)stream, tab, &mat)) return -1;
+  return render_impl<KIND_VFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, mat, v->dev);
+}
+
+// d(sum over views of sum adj_b * I_b)/d(Kd, Ks, Ke): ONE gradient of 3 x nT x 3
+// doubles, accumulated, every workgroup flushing into it; adj_dev: V full frames.
+static int views_adjoint_bounces(const RenderParams &p) {  // (checked first: a host-only scene reports it too)
+  if (p.max_bounces < 0 || p.max_bounces > kMaxAdjBounces) {
+    gpu_set_error("views adjoint: give max_bounces in 0..62 (the bounded estimator; the unbounded material adjoint keeps the scene's own camera)");
+    return -1;
+  }
+  return 0;
+}
+int gpu_adjoint_views(GpuScene *s, const GpuViews *v, RenderParams p, const float *kd_dev, const float *ks_dev,
+                      const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
+  if (views_adjoint_bounces(p) || views_params(s, v, p)) return -1;
+  return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream, v->dev);
+}
+
+// The rays of view `view` for n global sample indices (host arrays).
+int gpu_views_rays_host(GpuScene *s, const GpuViews *v, int view, RenderParams p, int64_t n, const int64_t *index,
+                        float *org, float *dir) {
+  RenderParams q = p;
+  if (views_params(s, v, q)) return -1;
+  if (view < 0 || view >= v->n) {
+    gpu_set_error("ipt_views_rays_host: view outside [0, n_views)");
+    return -1;
+  }
+  const uint64_t total = (uint64_t)p.width * (uint64_t)p.height * (uint64_t)p.spp;
+  for (int64_t i = 0; i < n; ++i)
+    if (index[i] < 0 || (uint64_t)index[i] >= total) {
+      gpu_set_error("ipt_views_rays_host: a sample index outside [0, width*height*spp)");
+      return -1;
+    }
+  if (n <= 0) return 0;
+  const TraceArgs a = make_args(s, p);  // rc_W, rc_H as the trace kernels get them
+  struct Buf {
+    void *p = nullptr;
+    ~Buf() {
+      if (p) (void)hipFree(p);
+    }
+  } ix, o, d;
+  const size_t n3 = (size_t)n * 3 * sizeof(float);
+  HIP_TRY(hipMalloc(&ix.p, (size_t)n * sizeof(int64_t)));
+  HIP_TRY(hipMalloc(&o.p, n3));
+  HIP_TRY(hipMalloc(&d.p, n3));
+  HIP_TRY(hipMemcpy(ix.p, index, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(view_rays_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, v->dev,
+                     view, p.width, p.height, p.spp, a.rc_W, a.rc_H, p.seed, n, (const int64_t *)ix.p, (float *)o.p,
+                     (float *)d.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(org, o.p, n3, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dir, d.p, n3, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // dL/dKd, dL/dKs, dL/dKe of the reference's own estimator (no bounce cap) in
@@ -2557,6 +2817,31 @@ int gpu_adjoint_mat_unbounded_host(GpuScene *s, const RenderParams &p, const flo
   HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
   if (gpu_adjoint_mat_unbounded(s, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
+  HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int gpu_render_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, float *hdr) {
+  RenderParams q = p;
+  if (views_params(s, v, q)) return -1;
+  const size_t n = (size_t)v->n * band_rows(p) * p.width * 3;
+  DevBuf h;
+  HIP_TRY(hipMalloc(&h.p, std::max<size_t>(n, 1) * sizeof(float)));
+  if (gpu_render_views(s, v, p, nullptr, nullptr, nullptr, (float *)h.p, nullptr)) return -1;
+  HIP_TRY(hipMemcpy(hdr, h.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int gpu_adjoint_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, const float *adj, double *grad) {
+  RenderParams q = p;
+  if (views_adjoint_bounces(p) || views_params(s, v, q)) return -1;
+  const size_t na = (size_t)v->n * p.width * p.height * 3, ng = (size_t)s->host.nT * 9;
+  DevBuf a, g;
+  HIP_TRY(hipMalloc(&a.p, na * sizeof(float)));
+  HIP_TRY(hipMalloc(&g.p, ng * sizeof(double)));
+  HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
+  if (gpu_adjoint_views(s, v, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
   HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }

@@ -647,9 +647,21 @@ bool load_mesh(const ObjectRecord &rec, std::vector<Tri> *tris, std::string *err
 }
 
 void camera_matrix(float M[16]) {  // Camera(CameraParams_t(true)), scene.h:15-84
-  const V3 eye{0.f, 0.f, 0.f}, look{0.f, 0.f, 1.f}, up0{0.f, 1.f, 0.f};
-  const float ha = static_cast<float>(M_PI * static_cast<double>(90.f) / static_cast<double>(360.f));
-  const float ar = 1.f;
+  const float eye[3] = {0.f, 0.f, 0.f}, look[3] = {0.f, 0.f, 1.f}, up[3] = {0.f, 1.f, 0.f};
+  camera_look_at(eye, look, up, 90.f, 1.f, M);
+}
+
+}  // namespace
+
+// Camera(CameraParams_t) + getInverseViewMatrix (scene.h:35-77) with the
+// reference's constants as arguments, in its unfused fp32 expression order.
+// As there, the eye lands in ROW 3 of the matrix (S * V^T), which
+// Ray::transform never reads: rays start at column 3 of rows 0..2.
+void camera_look_at(const float eye3[3], const float look3[3], const float up3[3], float fov_deg, float aspect,
+                    float M[16]) {
+  const V3 eye{eye3[0], eye3[1], eye3[2]}, look{look3[0], look3[1], look3[2]}, up0{up3[0], up3[1], up3[2]};
+  const float ha = static_cast<float>(M_PI * static_cast<double>(fov_deg) / static_cast<double>(360.f));
+  const float ar = aspect;
   V3 dir = hunit(look), up = hunit(up0);
   V3 f = hunit(dir);
   V3 s = hunit(hcross(f, up));
@@ -666,8 +678,6 @@ void camera_matrix(float M[16]) {  // Camera(CameraParams_t(true)), scene.h:15-8
     for (int j = 0; j < 4; ++j)  // S * V^T
       M[4 * i + j] = ((S[i][0] * V[j][0] + S[i][1] * V[j][1]) + S[i][2] * V[j][2]) + S[i][3] * V[j][3];
 }
-
-}  // namespace
 
 bool build_scene(const std::vector<ObjectRecord> &objects, HostScene *out, std::string *err) {
   std::vector<Tri> tris;

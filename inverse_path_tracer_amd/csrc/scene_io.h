@@ -53,6 +53,12 @@ struct HostScene {
 // and fills *err on failure (the reference exit(1)s instead).
 bool build_scene(const std::vector<ObjectRecord> &objects, HostScene *out, std::string *err);
 
+// The reference's camera matrix (scene.h:35-77) for caller-supplied eye, look
+// direction, up, height angle (degrees) and aspect ratio; HostScene::cam is
+// this with the reference's constants (0, +z, +y, 90, 1).
+void camera_look_at(const float eye[3], const float look[3], const float up[3], float fov_deg, float aspect,
+                    float M[16]);
+
 // Per-triangle export in the oracle's 57-float layout (for parity tests).
 void export_triangles(const HostScene &s, float *out);
 constexpr int kExportStride = 57;

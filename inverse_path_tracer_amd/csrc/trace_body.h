@@ -9,7 +9,9 @@
 // dL/dKe) and MATB (a forward whose
 // scene batch has one TriMat table per set), the parameters of
 // TraceKernArgs under their names, and tri_emit (MATG: triangle -> emitter
-// index or -1; nullptr otherwise).
+// index or -1; nullptr otherwise), and VIEWS (the sets of the grid split are
+// cameras over one material set, DESIGN.md §18: the view kernels' trailing
+// parameter is the views' table, read by its kernarg offset).
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   // scene batch: this workgroup's material set and its place among the set's blocks
@@ -18,15 +20,17 @@
   const uint32_t sgrid = a.nscenes > 1 ? (uint32_t)a.bps : gridDim.x;
   const uint64_t seed = a.seed + (uint64_t)set * a.seed_stride;
   if (a.nscenes > 1) {
-    kd += (size_t)set * 3 * a.nT;
+    // (VIEWS: the sets are views of ONE material set -- kd, mat, kd/pi and the
+    // gradient carry no per-set offset)
+    if (!VIEWS) kd += (size_t)set * 3 * a.nT;
     // per-set TriMat tables (0: one table for every set): the material
     // adjoint, and the forward instances of the material overrides' batch
-    if (MATG || MATB) mat += (size_t)set * a.mat_stride;
+    if (!VIEWS && (MATG || MATB)) mat += (size_t)set * a.mat_stride;
     if (is_fwd<MODE>()) out_samples += (size_t)set * a.out_stride;
     // (adj, grad: karg() at their uses, offset there; a set's gradient is
     // 3 nT doubles, or with MATG its [Kd | Ks | Ke] slice of 9 nT)
   }
-  const float *kdpi_g = a.kdpi_g ? a.kdpi_g + (size_t)set * 3 * a.nT : nullptr;
+  const float *kdpi_g = a.kdpi_g ? a.kdpi_g + (VIEWS ? (size_t)0 : (size_t)set * 3 * a.nT) : nullptr;
   constexpr int nthr = kBlock;
   const int nT = a.nT, nE = a.nE;
   const int vmax = a.rec_cap;  // ADJ record capacity per lane (ADJU: ring slots)
@@ -351,7 +355,10 @@
   // kInph (the in-phase refill): between the two, the current
   // group's pixel entries (kEntryWords each, 16-B aligned, by place q in the group)
   constexpr bool kInph = kInphase<MODE, BVH>();
-  constexpr bool kInphM = kInph && IPT_INPHASE_MERGE;  // 0: the entries only (A/B timing)
+  // (VIEWS: the merged block rotates camera rays by record nT of geom, the
+  // SCENE's camera -- the view instances keep the entries and refill at the
+  // loop top from the view's own matrix; same frames, §17.2)
+  constexpr bool kInphM = kInph && IPT_INPHASE_MERGE && !VIEWS;  // 0: the entries only (A/B timing)
   // kInphP: the sample taken in phase waits above the old path's item in the
   // one item word; else in a register of its own.  The SPEC instances spill
   // 16 B per lane with the register, the diffuse ones are 0.5% slower packed.
@@ -430,6 +437,20 @@
     const cst_args *apc = (const cst_args *)__builtin_amdgcn_kernarg_segment_ptr();  // first parameter: offset 0
     asm volatile("" : "+s"(apc));
     TraceArgs a = *apc;
+    if (VIEWS) {
+      // The view's camera and origin (19 floats of the views' table, the
+      // kernel's trailing parameter) in place of the scene's: wave-uniform,
+      // read through the constant address space like the kernarg copy above
+      // -- scalar loads from the scalar cache, taken again every iteration
+      // instead of 19 SGPRs held through the loop.
+      const cst_f32 *vq = (const cst_f32 *)karg<const float *>(sizeof(TraceKernArgs) + (MATG ? sizeof(void *) : 0)) +
+                          (size_t)set * kViewFloats;
+      asm volatile("" : "+s"(vq));
+#pragma unroll
+      for (int i = 0; i < 16; ++i) a.cam[i] = vq[i];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) a.cam_org[i] = vq[16 + i];
+    }
 #else
     TraceArgs a = ar;
 #endif
@@ -1317,7 +1338,7 @@
             }
             const int sl = a.grad_map ? a.grad_map[tk] : tk;
             const double v[3] = {(double)(ax * gk.x), (double)(ay * gk.y), (double)(az * gk.z)};
-            double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0);
+            double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (!VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0);
             bins_add(sl >= 0, grad, sl >= 0 ? (size_t)sl * 3 : (size_t)tk * 3, 3, v);
             if (MATG) {  // dL/dKs[tk], dL/dKe[et_k], dL/dKe[tri_0] (global layout [Kd | Ks | Ke], nT*3 each)
               const size_t gs3 = (size_t)a.grad_slots * 3;
@@ -1407,7 +1428,7 @@
   if (!is_fwd<MODE>()) {
     __syncthreads();
     if (n_acc > 0) {
-      double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0)
+      double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (!VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0)
                                     : edges;
       const int nb5 = (nT + 1) * nT * kEdgeL;
       for (int i = tid; i < n_acc; i += nthr) {

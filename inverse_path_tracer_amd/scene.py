@@ -347,6 +347,87 @@ class Scene:
                 "adjoint_materials_batch")
         return g.cpu().numpy()
 
+    # ---------------------------------------------------------- views (caller-supplied cameras)
+    @property
+    def camera_bound(self) -> float:
+        """The largest |component| a view's origin may have: the acceleration
+        structures are exact only inside the coordinate bound fixed at load
+        (ipt_scene_camera_bound); ``views`` refuses an origin beyond it."""
+        b = C.c_float(0)
+        N.check(N.lib().ipt_scene_camera_bound(self.handle, C.byref(b)), "camera_bound")
+        return float(b.value)
+
+    def views(self, cams) -> "Views":
+        """A handle on V cameras over this scene: cams is (V, 4, 4) float32 in
+        ``camera()``'s layout (``camera_look_at``, ``camera_at``).  Validated
+        once (NativeError: a non-finite or singular matrix, an origin beyond
+        ``camera_bound``); works on a host-only scene too (validation only)."""
+        return Views(self, cams)
+
+    def _views_dev(self, views, kd, ks, ke):
+        import torch
+
+        if views.scene is not self:
+            raise ValueError("the views belong to another scene")
+        dev = []
+        for name, v in (("kd", kd), ("ks", ks), ("ke", ke)):
+            if v is None:
+                dev.append(None)
+                continue
+            v = np.ascontiguousarray(np.asarray(v, np.float32))
+            if v.shape != (self.nT, 3):
+                raise ValueError("%s must be (nT=%d, 3), got %s" % (name, self.nT, v.shape))
+            dev.append(torch.from_numpy(v).cuda())
+        return torch, dev, [None if t is None else t.data_ptr() for t in dev]
+
+    def render_views(self, views, width, height, spp, max_bounces=None, seed=0, seed_stride=None, kd=None, ks=None,
+                     ke=None, row_begin=0, row_end=None, row_step=1):
+        """HDR images (V, rows, W, 3) of every view from ONE launch
+        (ipt_render_views_dev) with one material set: kd / ks / ke are (nT, 3)
+        host arrays or None (the scene's own).  View b traces seed + b *
+        seed_stride (default: one frame of samples, W*H*spp) and equals the
+        single-camera render through its camera bit for bit.  torch only
+        provides the device memory."""
+        torch, dev, ptr = self._views_dev(views, kd, ks, ke)
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        hdr = torch.zeros((len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
+        N.check(N.lib().ipt_render_views_dev(self.handle, views.handle, C.byref(p), stride, ptr[0], ptr[1], ptr[2],
+                                             hdr.data_ptr(), torch.cuda.current_stream(hdr.device).cuda_stream),
+                "render_views")
+        return hdr.cpu().numpy()
+
+    def adjoint_views(self, views, adj, width, height, spp, max_bounces, seed=0, seed_stride=None, kd=None, ks=None,
+                      ke=None, row_begin=0, row_end=None, row_step=1):
+        """d(sum over views of sum(adj[b] * I[b]))/d(Kd, Ks, Ke) as ONE
+        (3, nT, 3) float64 array from one launch (ipt_adjoint_views_dev); adj
+        is (V, H, W, 3) full frames.  Bounded estimator only."""
+        adj = np.ascontiguousarray(np.asarray(adj, np.float32))
+        if adj.shape != (len(views), height, width, 3):
+            raise ValueError("adj must be (V=%d, H=%d, W=%d, 3), got %s" % (len(views), height, width, adj.shape))
+        torch, dev, ptr = self._views_dev(views, kd, ks, ke)
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        a = torch.from_numpy(adj).cuda()
+        g = torch.zeros((3, self.nT, 3), device=a.device, dtype=torch.float64)
+        N.check(N.lib().ipt_adjoint_views_dev(self.handle, views.handle, C.byref(p), stride, ptr[0], ptr[1], ptr[2],
+                                              a.data_ptr(), g.data_ptr(),
+                                              torch.cuda.current_stream(a.device).cuda_stream), "adjoint_views")
+        return g.cpu().numpy()
+
+    def view_rays(self, views, view, width, height, spp, seed, sample_index):
+        """(origins, directions), (n, 3) float32 each: the camera rays of view
+        `view` for the global sample indices (pixel * spp + sample), from the
+        trace kernels' own generator and camera code (ipt_views_rays_host)."""
+        idx = np.ascontiguousarray(np.asarray(sample_index, np.int64).reshape(-1))
+        p = N.make_params(width, height, spp, 0, seed)
+        org = np.zeros((idx.size, 3), np.float32)
+        d = np.zeros((idx.size, 3), np.float32)
+        N.check(N.lib().ipt_views_rays_host(self.handle, views.handle, int(view), C.byref(p), idx.size,
+                                            idx.ctypes.data_as(C.POINTER(C.c_int64)), org.ctypes.data_as(N.fp),
+                                            d.ctypes.data_as(N.fp)), "view_rays")
+        return org, d
+
     def graph(self, target, width, height, spp, max_bounces=None, seed=0, row_begin=0, row_end=None, row_step=1):
         """createGraph: returns (acc[(nT+1)*nT, 8] float64, data[(nT+1)*nT*7] float32)."""
         p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
@@ -356,6 +437,58 @@ class Scene:
         N.check(N.lib().ipt_graph_host(self.handle, C.byref(p), target.ctypes.data_as(N.u8p),
                                        acc.ctypes.data_as(N.dp), data.ctypes.data_as(N.fp)), "graph")
         return acc, data
+
+
+def camera_look_at(eye, look, up, fov_deg=90.0, aspect=1.0) -> np.ndarray:
+    """The reference's camera matrix for (eye, look direction, up, height
+    angle in degrees, aspect ratio) as (4, 4) float32 (ipt_camera_look_at);
+    the defaults' matrix is ``Scene.camera()`` bit for bit.  As in the
+    reference the eye lands in row 3, which rays never read -- ``camera_at``
+    places a camera."""
+    v = [np.ascontiguousarray(np.asarray(a, np.float32).reshape(3)) for a in (eye, look, up)]
+    out = np.zeros(16, np.float32)
+    N.check(N.lib().ipt_camera_look_at(v[0].ctypes.data_as(N.fp), v[1].ctypes.data_as(N.fp),
+                                       v[2].ctypes.data_as(N.fp), float(fov_deg), float(aspect),
+                                       out.ctypes.data_as(N.fp)), "camera_look_at")
+    return out.reshape(4, 4)
+
+
+def camera_at(cam, origin) -> np.ndarray:
+    """A copy of the (4, 4) camera matrix whose rays start at `origin` (column
+    3 of rows 0..2, the position Ray::transform reads)."""
+    out = np.array(cam, np.float32).reshape(4, 4).copy()
+    out[:3, 3] = np.asarray(origin, np.float32).reshape(3)
+    return out
+
+
+class Views:
+    """V cameras over one scene (ipt_views_create): ``len()``, ``.cams``
+    ((V, 4, 4) float32, a copy), ``close()``."""
+
+    def __init__(self, scene: "Scene", cams):
+        cams = np.ascontiguousarray(np.asarray(cams, np.float32))
+        if cams.ndim == 2:
+            cams = cams[None]
+        if cams.ndim != 3 or cams.shape[1:] != (4, 4):
+            raise ValueError("cams must be (V, 4, 4), got %s" % (cams.shape,))
+        h = C.c_void_p(0)
+        N.check(N.lib().ipt_views_create(scene.handle, cams.shape[0], cams.ctypes.data_as(N.fp), C.byref(h)),
+                "views")
+        self.handle, self.scene, self.cams = h, scene, cams.copy()
+
+    def __len__(self):
+        return self.cams.shape[0]
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            N.lib().ipt_views_free(self.handle)
+            self.handle = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def compress(nT: int, acc: np.ndarray) -> np.ndarray:

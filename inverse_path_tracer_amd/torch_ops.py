@@ -303,3 +303,56 @@ def render_batch(scene: Scene, kd: torch.Tensor, width: int, height: int, spp: i
     stride = width * height * spp if seed_stride is None else int(seed_stride)
     p = N.make_params(width, height, spp, max_bounces, seed)
     return _BatchRenderFn.apply(kd, scene, p, stride, adjoint_seed)
+
+
+class _RenderViewsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kd, ks, ke, scene, views, params, stride, adjoint_seed):
+        given = [t for t in (kd, ks, ke) if t is not None]
+        dev = given[0].device
+        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
+        hdr = torch.empty((len(views), params.height, params.width, 3), device=dev, dtype=torch.float32)
+        N.check(N.lib().ipt_render_views_dev(scene.handle, views.handle, C.byref(params), stride, _ptr(c[0]),
+                                             _ptr(c[1]), _ptr(c[2]), hdr.data_ptr(), _stream(dev)),
+                "ipt_render_views_dev")
+        ctx.scene, ctx.views, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat = (scene, views, params, stride,
+                                                                                  adjoint_seed, c)
+        return hdr
+
+    @staticmethod
+    def backward(ctx, grad_hdr):
+        p = _replay_params(ctx.params, ctx.adjoint_seed)
+        kd, ks, ke = ctx.mat
+        adj = grad_hdr.float().contiguous()
+        g = torch.zeros((3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
+        N.check(N.lib().ipt_adjoint_views_dev(ctx.scene.handle, ctx.views.handle, C.byref(p), ctx.stride, _ptr(kd),
+                                              _ptr(ks), _ptr(ke), adj.data_ptr(), g.data_ptr(), _stream(adj.device)),
+                "ipt_adjoint_views_dev")
+        out = [g[i].float() if (t is not None and ctx.needs_input_grad[i]) else None
+               for i, t in enumerate((kd, ks, ke))]
+        return out[0], out[1], out[2], None, None, None, None, None
+
+
+def render_views(scene: Scene, views, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4, seed: int = 0,
+                 seed_stride=None, adjoint_seed=None) -> torch.Tensor:
+    """``render_materials`` through V caller-supplied cameras (``scene.views``)
+    with ONE material set: kd, ks, ke are (nT, 3) CUDA tensors (any may be
+    None = the scene's own, or not require grad; at least one is given) ->
+    HDR images (V, H, W, 3).  ONE forward launch (ipt_render_views_dev): view
+    b is ``render_materials`` through camera b at ``seed + b * seed_stride``
+    bit for bit (default stride: one frame of samples, W*H*spp).  The backward
+    is ONE launch of the views' material adjoint, the gradient summed over the
+    views, returned as float32 for the inputs that require it.  Bounded
+    estimator only (max_bounces 0..62).  `adjoint_seed` as in ``render``."""
+    given = [t for t in (kd, ks, ke) if t is not None]
+    if not given:
+        raise ValueError("render_views needs at least one of kd, ks, ke as a device tensor")
+    for t in given:
+        if tuple(t.shape) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+    if max_bounces is None or max_bounces < 0:
+        raise N.NativeError("views adjoint: the unbounded estimator (max_bounces < 0) is not supported by "
+                            "render_views; give max_bounces in 0..62")
+    stride = width * height * spp if seed_stride is None else int(seed_stride)
+    p = N.make_params(width, height, spp, max_bounces, seed)
+    return _RenderViewsFn.apply(kd, ks, ke, scene, views, p, stride, adjoint_seed)
