@@ -36,6 +36,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "bvh.h"
@@ -277,7 +278,7 @@ struct TraceArgs {
   const float4 *bvh_wide;  // WideNode or QWideNode records (kWideF4 float4 each)
   const TriIsect *bvh_wtris;
   int bvh_wide_lds, coop_stride;
-  int bvh_big_lds;  // culled path pre-pass: the large pairs' LDS copy is built (launch_bvh chooses)
+  int bvh_big_lds;  // culled path pre-pass: the large pairs' LDS copy is built (launch_bvh_pick chooses)
   float root_box[6];
   float tree_sphere[4];     // bvh.cpp tree_cull
   const float4 *src_cull;   // per triangle {face normal, tau} (ipt_device.h tree_skip)
@@ -1063,6 +1064,59 @@ static std::vector<double> pmf_reciprocals(const std::vector<float> &pmf) {
   return r;
 }
 
+// The kernel a launch runs: trace_kernel<MODE, SPEC, BVH>, or the material
+// adjoint (MODE_ADJ: trace_mat_kernel<SPEC, BVH>, MODE_ADJU: the unbounded
+// trace_matu_kernel<SPEC, BVH>), or (the forwards only) the batch forward with
+// per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
+// KIND_VFWD / KIND_VMAT: the views' forward and bounded material adjoint
+// (trace_fwd_views_kernel, trace_mat_views_kernel; DESIGN.md §18).
+enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4 };
+constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }
+// The (MODE, KIND) pairs that have kernels (kernel_of's static_asserts).
+constexpr bool inst_valid(int mode, int kind) {
+  return kind == KIND_TRACE  ? mode >= MODE_FWD && mode <= MODE_ADJW
+         : kind == KIND_MATG ? mode == MODE_ADJ || mode == MODE_ADJU
+         : kind == KIND_VMAT ? mode == MODE_ADJ
+                             : mode == MODE_FWD || mode == MODE_FWDM;
+}
+// An instance's slot in GpuScene::inst.  0..23: trace_kernel<mode, spec, bvh>;
+// 24..27: trace_mat_kernel<spec, bvh>; 28..35: trace_fwd_mat_kernel<FWD | FWDM,
+// spec, bvh>; 36..39: trace_matu_kernel<spec, bvh>; 40..47:
+// trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh>.
+constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
+  return (kind == KIND_MATG   ? (mode == MODE_ADJU ? 36 : 24)
+          : kind == KIND_FWDB ? 28 + (mode == MODE_FWDM ? 4 : 0)
+          : kind == KIND_VFWD ? 40 + (mode == MODE_FWDM ? 4 : 0)
+          : kind == KIND_VMAT ? 48
+                              : mode * 4) +
+         (spec ? 2 : 0) + (bvh ? 1 : 0);
+}
+// One past the largest slot of a valid instance, or -1 when two share a slot.
+constexpr int inst_slot_count() {
+  uint64_t seen = 0;
+  int n = 0;
+  for (int kind = KIND_TRACE; kind <= KIND_VMAT; ++kind)
+    for (int mode = MODE_FWD; mode <= MODE_ADJW; ++mode)
+      for (int sb = 0; sb < 4 && inst_valid(mode, kind); ++sb) {
+        const int slot = inst_slot(mode, (sb & 2) != 0, (sb & 1) != 0, kind);
+        if (slot < 0 || slot >= 64 || (seen >> slot & 1)) return -1;
+        seen |= 1ull << slot;
+        n = slot + 1 > n ? slot + 1 : n;
+      }
+  return n;
+}
+constexpr int kInstSlots = inst_slot_count();
+static_assert(kInstSlots > 0, "two instances share a slot of GpuScene::inst (inst_slot)");
+
+// What the launch path remembers per kernel instance and scene.
+struct InstCache {
+  int grid = 0;  // resident workgroups (0 = not queried) ...
+  size_t grid_lds = 0;  // ... for this many bytes of LDS per workgroup (resident_grid)
+  size_t pick_base = 0;  // launch_bvh_pick's choice of LDS extras (kept in the BVH = false slot): base bytes it was made for
+  size_t pick_tail = 0;  // ... and the per-block tail (fused pixel mean slots) behind it
+  int pick_opt = -1;     // ... the choice (-1 = not made)
+};
+
 struct GpuScene {
   HostScene host;
   int device = 0;
@@ -1092,15 +1146,7 @@ struct GpuScene {
   int matu_nl = 0;       // ... for its LDS base
   int *grad_map = nullptr, *slot_tri = nullptr;  // ADJ hot-set LDS slots (large scenes)
   int *tri_emit = nullptr;  // triangle -> emitter index or -1 (material overrides and adjoint)
-  // slots 0..23: trace_kernel<mode, spec, bvh>; 24..27: trace_mat_kernel<spec, bvh>;
-  // 28..35: trace_fwd_mat_kernel<FWD | FWDM, spec, bvh>; 36..39: trace_matu_kernel<spec, bvh>;
-  // 40..47: trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh> (inst_slot)
-  int grid[52] = {0};       // resident workgroups per instance (0 = not queried)
-  size_t grid_lds[52] = {0};
-  size_t pick_base[52] = {0};  // launch_bvh's LDS choice per (mode, spec): base bytes it was made for
-  size_t pick_tail[52] = {0};  // ... and the per-block tail (fused pixel mean slots) behind it
-  int pick_opt[52] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                      -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  InstCache inst[kInstSlots];  // by inst_slot()
   // dynamic-chunk counters per stream (stream_counters): `words` grab words,
   // zeroed once; every launch leaves them zero (TraceArgs::chunk_ctr)
   struct Counters {
@@ -1313,76 +1359,64 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 #ifndef IPT_DEBUG_GRID
 #define IPT_DEBUG_GRID 0
 #endif
-// The kernel a launch runs: trace_kernel<MODE, SPEC, BVH>, or the material
-// adjoint (MODE_ADJ: trace_mat_kernel<SPEC, BVH>, MODE_ADJU: the unbounded
-// trace_matu_kernel<SPEC, BVH>), or (the forwards only) the batch forward with
-// per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
-// KIND_VFWD / KIND_VMAT: the views' forward and bounded material adjoint
-// (trace_fwd_views_kernel, trace_mat_views_kernel; DESIGN.md §18).
-enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4 };
-constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }
-// The kernel of (MODE, SPEC, BVH, KIND), for the occupancy queries.
+// The one table of trace kernels: the __global__ of (MODE, SPEC, BVH, KIND).
+// Occupancy queries and the launch itself go through it.
 template <int MODE, bool SPEC, bool BVH, int KIND>
-constexpr auto views_kernel() {
+constexpr auto kernel_of() {
   if constexpr (KIND == KIND_VMAT) {
     static_assert(MODE == MODE_ADJ, "the views' adjoint is the bounded material adjoint");
     return &trace_mat_views_kernel<SPEC, BVH>;
-  } else {
+  } else if constexpr (KIND == KIND_VFWD) {
+    static_assert(is_fwd<MODE>(), "the views' forward: forward instances only");
     return &trace_fwd_views_kernel<MODE, SPEC, BVH>;
+  } else if constexpr (KIND == KIND_MATG) {
+    static_assert(MODE == MODE_ADJ || MODE == MODE_ADJU, "the material adjoint is MODE_ADJ or MODE_ADJU");
+    if constexpr (MODE == MODE_ADJU) return &trace_matu_kernel<SPEC, BVH>;
+    else return &trace_mat_kernel<SPEC, BVH>;
+  } else if constexpr (KIND == KIND_FWDB) {
+    static_assert(is_fwd<MODE>(), "the batch forward: forward instances only");
+    return &trace_fwd_mat_kernel<MODE, SPEC, BVH>;
+  } else {
+    return &trace_kernel<MODE, SPEC, BVH>;
   }
 }
-// The material adjoint's kernel for MODE (KIND_MATG).
-template <int MODE, bool SPEC, bool BVH>
-constexpr auto matg_kernel() {
-  static_assert(MODE == MODE_ADJ || MODE == MODE_ADJU, "the material adjoint is MODE_ADJ or MODE_ADJU");
-  if constexpr (MODE == MODE_ADJU) return &trace_matu_kernel<SPEC, BVH>;
-  else return &trace_mat_kernel<SPEC, BVH>;
+// ... and its name, for the IPT_DEBUG_GRID prints.
+constexpr const char *kernel_name(int mode, int kind) {
+  return kind == KIND_VFWD   ? "trace_fwd_views_kernel"
+         : kind == KIND_VMAT ? "trace_mat_views_kernel"
+         : kind == KIND_MATG ? (mode == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
+         : kind == KIND_FWDB ? "trace_fwd_mat_kernel"
+                             : "trace_kernel";
 }
-// An instance's slot in GpuScene's per-instance caches.
 template <int MODE, bool SPEC, bool BVH, int KIND>
-constexpr int inst_slot() {
-  return (KIND == KIND_MATG   ? (MODE == MODE_ADJU ? 36 : 24)
-          : KIND == KIND_FWDB ? 28 + (MODE == MODE_FWDM ? 4 : 0)
-          : KIND == KIND_VFWD ? 40 + (MODE == MODE_FWDM ? 4 : 0)
-          : KIND == KIND_VMAT ? 48
-                              : MODE * 4) +
-         (SPEC ? 2 : 0) + (BVH ? 1 : 0);
-}
-template <int MODE, bool SPEC, bool BVH, int KIND = KIND_TRACE>
 static int resident_grid(GpuScene *s, size_t lds_bytes, int *grid) {
-  const int slot = inst_slot<MODE, SPEC, BVH, KIND>();
-  if (s->grid[slot] == 0 || s->grid_lds[slot] != lds_bytes) {
+  InstCache &c = s->inst[inst_slot(MODE, SPEC, BVH, KIND)];
+  if (c.grid == 0 || c.grid_lds != lds_bytes) {
     int per_cu = 0, cus = 0;
-    if constexpr (kind_views(KIND)) {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, views_kernel<MODE, SPEC, BVH, KIND>(), kBlock,
-                                                           lds_bytes));
-    } else if constexpr (KIND == KIND_MATG) {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, matg_kernel<MODE, SPEC, BVH>(), kBlock, lds_bytes));
-    } else if constexpr (KIND == KIND_FWDB) {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, BVH>, kBlock,
-                                                           lds_bytes));
-    } else {
-      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<MODE, SPEC, BVH>, kBlock,
-                                                           lds_bytes));
-    }
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of<MODE, SPEC, BVH, KIND>(), kBlock, lds_bytes));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
     if (per_cu <= 0) {
       gpu_set_error("trace kernel cannot be resident (LDS request too large?)");
       return -1;
     }
-    s->grid[slot] = per_cu * cus;
-    s->grid_lds[slot] = lds_bytes;
+    c.grid = per_cu * cus;
+    c.grid_lds = lds_bytes;
     if (IPT_DEBUG_GRID)  // (make variant DEFS=-DIPT_DEBUG_GRID=1)
-      std::fprintf(stderr, "[ipt] %s<%d,%d,%d>: %zu B LDS/block, %d blocks/CU x %d CUs\n",
-                   KIND == KIND_VFWD   ? "trace_fwd_views_kernel"
-                   : KIND == KIND_VMAT ? "trace_mat_views_kernel"
-                   : KIND == KIND_MATG ? (MODE == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
-                   : KIND == KIND_FWDB ? "trace_fwd_mat_kernel"
-                                       : "trace_kernel",
-                   MODE, (int)SPEC, (int)BVH, lds_bytes, per_cu, cus);
+      std::fprintf(stderr, "[ipt] %s<%d,%d,%d>: %zu B LDS/block, %d blocks/CU x %d CUs\n", kernel_name(MODE, KIND), MODE,
+                   (int)SPEC, (int)BVH, lds_bytes, per_cu, cus);
   }
-  *grid = s->grid[slot];
+  *grid = c.grid;
   return 0;
+}
+
+// camera_ray's origin M * (0,0,0,1) per row, with its own operations (fmaf is
+// the IEEE fma on host and device), evaluated once: for the scene's camera
+// (make_args) and for each entry of a views' table (gpu_views_create).
+static void camera_origin(const float *cam, float *org) {
+  for (int i = 0; i < 3; ++i) {
+    const float *M = cam + 4 * i;
+    org[i] = std::fmaf(M[3], 1.f, std::fmaf(M[2], 0.f, std::fmaf(M[1], 0.f, M[0] * 0.f)));
+  }
 }
 
 static TraceArgs make_args(const GpuScene *s, const RenderParams &p);
@@ -1396,7 +1430,11 @@ static TraceArgs make_args_scene(const GpuScene *s) {
   return make_args(s, p);
 }
 static TraceArgs make_args(const GpuScene *s, const RenderParams &p) {
-  TraceArgs a;
+  // Everything not written here is zero / nullptr: the BVH fields and
+  // big_pomask (set together, bvh_lds), the gradient bins (adjoint_args),
+  // mat_stride and kdpi_g (launch()), the chunk sizes, counters and ADJU ring
+  // (launch_inst), the fused pixel mean's fields (render_impl).
+  TraceArgs a = TraceArgs();
   a.W = p.width;
   a.H = p.height;
   a.spp = p.spp;
@@ -1406,9 +1444,6 @@ static TraceArgs make_args(const GpuScene *s, const RenderParams &p) {
   a.n_samples = (uint64_t)rows * p.width * p.spp;
   a.nT = s->host.nT;
   a.nE = s->host.nE;
-  a.lds_edges = 0;
-  a.sample_major = 0;
-  a.kdpi_g = nullptr;
   a.kd_tables = s->host.nT <= kMaxTableTris ? 1 : 0;
   a.small_pairs = s->host.nT <= 2 * kSmallPairs ? 1 : 0;
   a.npix = (uint64_t)rows * p.width;
@@ -1419,56 +1454,23 @@ static TraceArgs make_args(const GpuScene *s, const RenderParams &p) {
   a.m_spp = p.spp > 1 ? ~0ull / (uint64_t)p.spp + 1 : 0;
   a.m_W = p.width > 1 ? ~0ull / (uint64_t)p.width + 1 : 0;
   a.m_npix = a.npix > 1 ? ~0ull / a.npix + 1 : 0;
-  a.bvh_nbig = 0;
-  a.bvh_big = nullptr;
-  a.bvh_big_idx = nullptr;
-  a.bvh_big_boxes = nullptr;
-  a.bvh_wide = nullptr;
-  a.bvh_wtris = nullptr;
-  a.bvh_wide_lds = 0;
-  a.bvh_big_lds = 0;
-  a.coop_stride = 0;
   for (int k = 0; k < 6; ++k) a.root_box[k] = s->host.bvh_root_box[k];
   for (int k = 0; k < 4; ++k) a.tree_sphere[k] = s->host.bvh_sphere[k];
   a.src_cull = s->src_cull;
-  a.grad_slots = 0;
-  a.grad_map = nullptr;
-  a.slot_tri = nullptr;
   std::memcpy(a.cam, s->host.cam, sizeof a.cam);
   a.emit_pmfr = s->emit_pmfr;
-  for (int i = 0; i < 3; ++i) {  // camera_ray's pr[i], evaluated once: fmaf is the IEEE fma on host and device
-    const float *M = a.cam + 4 * i;
-    a.cam_org[i] = std::fmaf(M[3], 1.f, std::fmaf(M[2], 0.f, std::fmaf(M[1], 0.f, M[0] * 0.f)));
-  }
+  camera_origin(a.cam, a.cam_org);  // camera_ray's pr[i], evaluated once
   a.rec_cap = p.max_bounces >= 0 ? p.max_bounces + 1 : 0;
-  a.rec_lds = 0;
-  a.grec = nullptr;
-  a.grec_stride = 0;
-  a.pool_chunks = 0;
-  a.mring = nullptr;
-  a.chunk = 0;
-  a.group = 0;
-  a.chunk_small = 0;
-  a.chunk_big_n = 0;
-  a.chunk_ctr = nullptr;
-  a.grabs = 0;
   a.pboxes = s->pboxes;
   a.pomask = s->host.nE > 0 ? s->pomask : nullptr;
-  a.big_pomask = nullptr;  // set with the other BVH fields (bvh_lds)
   a.nscenes = p.nscenes > 1 ? p.nscenes : 1;
   a.bps = 1;
-  a.mat_stride = 0;  // launch(): nT for a batch with its own TriMat tables
   a.seed_stride = p.seed_stride;
   a.out_stride = a.n_samples * 3;
   a.adj_stride = (uint64_t)p.width * p.height * 3;
   a.rc_spp = (p.spp > 0 && p.spp <= (1 << 24) && (p.spp & (p.spp - 1)) == 0) ? 1.0f / (float)p.spp : 0.f;
   a.rc_W = (p.width > 0 && (p.width & (p.width - 1)) == 0) ? 1.0f / (float)p.width : 0.f;
   a.rc_H = (p.height > 0 && (p.height & (p.height - 1)) == 0) ? 1.0f / (float)p.height : 0.f;
-  a.fused = 0;
-  a.mean_off = 0;
-  a.mean_wstride = 0;
-  a.nslots = 0;
-  a.ldr = nullptr;
   return a;
 }
 
@@ -1480,6 +1482,9 @@ static bool use_bvh(const GpuScene *s) {
   if (s->accel == IPT_ACCEL_BRUTE) return false;
   return s->host.nT >= kBvhMinTris;
 }
+
+// trace_kernel's lane_ws: six words per lane (the BVH forwards, and MODE_ADJW with IPT_ADJW_LANE_LDS)
+constexpr size_t kLaneWsBytes = (size_t)6 * kBlock * sizeof(uint32_t);
 
 // BVH LDS carve-out on top of `base` bytes; fills the args' BVH fields:
 // [wide nodes if staged][large pairs' plane offsets][large pairs' copy if
@@ -1500,8 +1505,7 @@ static size_t bvh_lds(const GpuScene *s, TraceArgs &a, size_t base, bool stage =
   const size_t head = bvh_lds_offset(base) + (size_t)a.bvh_wide_lds * kWideF4 * sizeof(float4) +
                       (size_t)a.bvh_nbig * 6 * sizeof(float) + (a.bvh_big_lds ? big_lds_bytes(a.bvh_nbig) : 0) +
                       emit_lds_bytes(s->host.nE);
-  return head + (size_t)(kBlock / 64) * 8 * a.coop_stride * sizeof(uint32_t) +
-         (lane_words ? (size_t)6 * kBlock * sizeof(uint32_t) : 0);  // (BVH forward: trace_kernel's lane_ws)
+  return head + (size_t)(kBlock / 64) * 8 * a.coop_stride * sizeof(uint32_t) + (lane_words ? kLaneWsBytes : 0);
 }
 
 static size_t table_bytes(const TraceArgs &a) {
@@ -1614,12 +1618,24 @@ static uint32_t launch_grabs(bool guided, uint64_t units, uint64_t c, uint64_t s
 #define IPT_DYN_SMALL_CHUNK 64
 #endif
 
-// mat_dev: the launch's TriMat table (nullptr: the scene's own; the material
-// overrides pass the table pack_mat_kernel wrote).
-template <int MODE, bool SPEC, bool BVH, int KIND = KIND_TRACE>
-static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float *kd_dev, float *out, const float *adj,
-                       double *grad, const uint8_t *target, double *edges, hipStream_t st,
-                       const TriMat *mat_dev = nullptr, const float *views_dev = nullptr) {
+// What a launch reads and writes besides the scene, by name; whatever a kind
+// of launch does not use stays null.
+struct LaunchIO {
+  const float *kd = nullptr;  // albedo (nullptr: the scene's own)
+  float *out = nullptr;       // forwards: samples, or the HDR images of the fused render
+  const float *adj = nullptr;  // adjoints: dL/dI ...
+  double *grad = nullptr;      // ... and their gradient
+  const uint8_t *target = nullptr;  // graph: target image ...
+  double *edges = nullptr;          // ... and bins
+  const TriMat *mat = nullptr;  // TriMat table (nullptr: the scene's own; the overrides pass what pack_mat_kernel wrote)
+  const float *views = nullptr;  // KIND_VFWD / KIND_VMAT: the views' table
+  hipStream_t stream = nullptr;
+  size_t tail = 0;  // bytes per workgroup behind everything else (16-B aligned; the fused pixel mean's slots, TraceArgs::mean_off)
+};
+
+template <int MODE, bool SPEC, bool BVH, int KIND>
+static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const LaunchIO &io) {
+  const hipStream_t st = io.stream;
   int grid = 0;
   if (lds > 160 * 1024) {
     gpu_set_error("LDS footprint of the launch exceeds 160 KiB");
@@ -1691,27 +1707,26 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const float 
     gpu_set_error("launch failed on request (ipt_debug_fail_launches)");
     return -1;
   }
-  const TriMat *mat = mat_dev ? mat_dev : s->mat;
-  if constexpr (KIND == KIND_VMAT)
-    hipLaunchKernelGGL((trace_mat_views_kernel<SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs,
-                       s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad,
-                       target, edges, s->tri_emit, views_dev);
-  else if constexpr (KIND == KIND_VFWD)
-    hipLaunchKernelGGL((trace_fwd_views_kernel<MODE, SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect,
-                       s->pairs, s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out,
-                       adj, grad, target, edges, views_dev);
-  else if constexpr (KIND == KIND_MATG)
-    hipLaunchKernelGGL((matg_kernel<MODE, SPEC, BVH>()), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs, s->geom,
-                       mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad, target,
-                       edges, s->tri_emit);
-  else if constexpr (KIND == KIND_FWDB)
-    hipLaunchKernelGGL((trace_fwd_mat_kernel<MODE, SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect,
-                       s->pairs, s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out,
-                       adj, grad, target, edges);
-  else
-    hipLaunchKernelGGL((trace_kernel<MODE, SPEC, BVH>), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs,
-                       s->geom, mat, kd_dev ? kd_dev : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf, out, adj, grad,
-                       target, edges);
+  if (IPT_DEBUG_GRID)  // every number of the launch the host decides (no pointers)
+    std::fprintf(stderr,
+                 "[ipt] launch %s<%d,%d,%d> grid=%d lds=%zu bps=%d chunk=%u chunk_small=%u chunk_big_n=%u grabs=%u group=%u "
+                 "rec_cap=%d rec_lds=%d pool_chunks=%d grec_stride=%llu grad_slots=%d bvh_wide_lds=%d bvh_big_lds=%d "
+                 "coop_stride=%d mean_off=%u mean_wstride=%u nslots=%d mat_stride=%u kd_tables=%d small_pairs=%d "
+                 "sample_major=%d\n",
+                 kernel_name(MODE, KIND), MODE, (int)SPEC, (int)BVH, grid, lds, b.bps, b.chunk, b.chunk_small,
+                 b.chunk_big_n, b.grabs, b.group, b.rec_cap, b.rec_lds, b.pool_chunks, (unsigned long long)b.grec_stride,
+                 b.grad_slots, b.bvh_wide_lds, b.bvh_big_lds, b.coop_stride, b.mean_off, b.mean_wstride, b.nslots,
+                 b.mat_stride, b.kd_tables, b.small_pairs, b.sample_major);
+  // the parameters every trace kernel takes, then its own trailing ones
+  auto enqueue = [&](auto... trailing) {
+    hipLaunchKernelGGL((kernel_of<MODE, SPEC, BVH, KIND>()), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs,
+                       s->geom, io.mat ? io.mat : s->mat, io.kd ? io.kd : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf,
+                       io.out, io.adj, io.grad, io.target, io.edges, trailing...);
+  };
+  if constexpr (KIND == KIND_VMAT) enqueue(s->tri_emit, io.views);
+  else if constexpr (KIND == KIND_VFWD) enqueue(io.views);
+  else if constexpr (KIND == KIND_MATG) enqueue(s->tri_emit);
+  else enqueue();
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1733,27 +1748,19 @@ __global__ __launch_bounds__(kBlock) void kdpi_kernel(const float *__restrict__ 
 // resident workgroups per CU.  North-star adjoint: the tree stage + records +
 // bins sit just under 3 workgroups/CU, and the pair copy would tip it to 2
 // (6.6 -> 7.9 ms).  Cached per scene and instance for the base LDS bytes.
-template <int MODE, bool SPEC, int KIND = KIND_TRACE>
+template <int MODE, bool SPEC, int KIND>
 static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) {
-  const int slot = inst_slot<MODE, SPEC, false, KIND>();
+  InstCache &c = s->inst[inst_slot(MODE, SPEC, false, KIND)];
   const bool opt[4][2] = {{true, true}, {true, false}, {false, true}, {false, false}};
   const size_t base = *lds;
-  if (s->pick_opt[slot] < 0 || s->pick_base[slot] != base || s->pick_tail[slot] != tail) {
+  if (c.pick_opt < 0 || c.pick_base != base || c.pick_tail != tail) {
     int best = -1, best_per_cu = 0;
     for (int k = 0; k < 4; ++k) {
       TraceArgs b = a;
       const size_t l = bvh_lds_offset(bvh_lds(s, b, base, opt[k][0], opt[k][1], is_fwd<MODE>())) + tail;
       if (l > 160 * 1024) continue;
       int per_cu = 0;
-      if constexpr (kind_views(KIND)) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, views_kernel<MODE, SPEC, true, KIND>(), kBlock, l));
-      } else if constexpr (KIND == KIND_MATG) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, matg_kernel<MODE, SPEC, true>(), kBlock, l));
-      } else if constexpr (KIND == KIND_FWDB) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fwd_mat_kernel<MODE, SPEC, true>, kBlock, l));
-      } else {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel<MODE, SPEC, true>, kBlock, l));
-      }
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_of<MODE, SPEC, true, KIND>(), kBlock, l));
       if (per_cu > best_per_cu) {
         best = k;
         best_per_cu = per_cu;
@@ -1763,69 +1770,60 @@ static int launch_bvh_pick(GpuScene *s, TraceArgs &a, size_t *lds, size_t tail) 
       gpu_set_error("BVH trace kernel cannot be resident (LDS request too large?)");
       return -1;
     }
-    s->pick_opt[slot] = best;
-    s->pick_base[slot] = base;
-    s->pick_tail[slot] = tail;
+    c.pick_opt = best;
+    c.pick_base = base;
+    c.pick_tail = tail;
   }
-  const int k = s->pick_opt[slot];
+  const int k = c.pick_opt;
   *lds = bvh_lds(s, a, base, opt[k][0], opt[k][1], is_fwd<MODE>());
   return 0;
 }
 
-// tail: bytes per workgroup placed after everything else (16-B aligned; the
-// fused pixel mean's sample slots, TraceArgs::mean_off).
+// One launch: `a` as the entry point filled it, `lds` its bytes before the
+// BVH carve-out and the tail.  SPEC and BVH are chosen here, once.
 template <int MODE, int KIND = KIND_TRACE>
-static int launch(GpuScene *s, TraceArgs a, size_t lds, const float *kd_dev, float *out, const float *adj,
-                  double *grad, const uint8_t *target, double *edges, hipStream_t st, size_t tail = 0,
-                  const TriMat *mat_dev = nullptr, const float *views_dev = nullptr) {
+static int launch(GpuScene *s, TraceArgs a, size_t lds, const LaunchIO &io) {
+  const hipStream_t st = io.stream;
   // a batch's per-launch table holds one TriMat table per set (pack_materials);
   // its forward runs the instances that offset mat per set
   // (views: one table, one kd for every set)
-  a.mat_stride = (mat_dev && a.nscenes > 1 && !kind_views(KIND)) ? (uint32_t)a.nT : 0u;
+  a.mat_stride = (io.mat && a.nscenes > 1 && !kind_views(KIND)) ? (uint32_t)a.nT : 0u;
   if constexpr (is_fwd<MODE>() && KIND == KIND_TRACE) {
-    if (a.mat_stride)
-      return launch<MODE, KIND_FWDB>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, tail, mat_dev);
+    if (a.mat_stride) return launch<MODE, KIND_FWDB>(s, a, lds, io);
   }
   StreamScratch kdpi;
   if (MODE != MODE_GRAPH && !a.kd_tables && a.n_samples > 0) {
     const int n = 3 * s->host.nT * (kind_views(KIND) ? 1 : a.nscenes);
     if (kdpi.alloc((size_t)n * sizeof(float), st)) return -1;
-    hipLaunchKernelGGL(kdpi_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, kd_dev ? kd_dev : s->kd, n,
+    hipLaunchKernelGGL(kdpi_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, io.kd ? io.kd : s->kd, n,
                        (float *)kdpi.p);
     HIP_TRY(hipGetLastError());
     a.kdpi_g = (const float *)kdpi.p;
   }
-  auto add_tail = [&]() {
-    if (tail) {
+  auto run = [&](auto spec, auto bvh) {  // the instance: LDS extras of the BVH, then the tail, then the launch
+    constexpr bool SPEC = decltype(spec)::value, BVH = decltype(bvh)::value;
+    if constexpr (BVH) {
+      if (launch_bvh_pick<MODE, SPEC, KIND>(s, a, &lds, io.tail)) return -1;
+    }
+    if (io.tail) {
       a.mean_off = (uint32_t)bvh_lds_offset(lds);
-      lds = a.mean_off + tail;
+      lds = a.mean_off + io.tail;
     }
+    return launch_inst<MODE, SPEC, BVH, KIND>(s, a, lds, io);
   };
-  if constexpr (MODE == MODE_ADJW) {  // (gpu_adjoint: brute-force diffuse scenes only)
-    add_tail();
-    return launch_inst<MODE, false, false>(s, a, lds, kd_dev, out, adj, grad, target, edges, st);
-  } else if (use_bvh(s)) {
-    if (s->has_ks) {
-      if (launch_bvh_pick<MODE, true, KIND>(s, a, &lds, tail)) return -1;
-      add_tail();
-      return launch_inst<MODE, true, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
-    }
-    if (launch_bvh_pick<MODE, false, KIND>(s, a, &lds, tail)) return -1;
-    add_tail();
-    return launch_inst<MODE, false, true, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
-  } else {
-    add_tail();
-    if (s->has_ks)
-      return launch_inst<MODE, true, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
-    return launch_inst<MODE, false, false, KIND>(s, a, lds, kd_dev, out, adj, grad, target, edges, st, mat_dev, views_dev);
-  }
+  constexpr std::true_type yes;
+  constexpr std::false_type no;
+  if constexpr (MODE == MODE_ADJW) return run(no, no);  // (gpu_adjoint: brute-force diffuse scenes only)
+  else if (use_bvh(s)) return s->has_ks ? run(yes, yes) : run(no, yes);
+  else return s->has_ks ? run(yes, no) : run(no, no);
 }
 
 int gpu_render_samples(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev, void *stream) {
   if (check_params(s, p)) return -1;
   const TraceArgs a = make_args(s, p);
-  return launch<MODE_FWD>(s, a, table_bytes(a), kd_dev, samples_dev, nullptr, nullptr, nullptr, nullptr,
-                          (hipStream_t)stream);
+  LaunchIO io;
+  io.kd = kd_dev, io.out = samples_dev, io.stream = (hipStream_t)stream;
+  return launch<MODE_FWD>(s, a, table_bytes(a), io);
 }
 
 int gpu_pixel_mean(const float *samples_dev, int64_t npix, int spp, float *hdr_dev, uint8_t *ldr_dev, void *stream) {
@@ -1843,8 +1841,9 @@ static int render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd
   if (check_params(s, p)) return -1;
   TraceArgs a = make_args(s, p);
   a.sample_major = 1;
-  return launch<MODE_FWD, KIND>(s, a, table_bytes(a), kd_dev, samples_dev, nullptr, nullptr, nullptr, nullptr,
-                                (hipStream_t)stream, 0, mat_dev, views_dev);
+  LaunchIO io;
+  io.kd = kd_dev, io.out = samples_dev, io.mat = mat_dev, io.views = views_dev, io.stream = (hipStream_t)stream;
+  return launch<MODE_FWD, KIND>(s, a, table_bytes(a), io);
 }
 int gpu_render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev,
                           void *stream) {
@@ -1945,9 +1944,10 @@ static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, 
                                 3 * fs.slots * p.spp + 3) & ~3u;
     a.ldr = ldr_dev;
     a.out_stride = (uint64_t)npix * 3;  // per material set: its own HDR (and LDR) image
-    const size_t tail = (size_t)(kBlock / 64) * a.mean_wstride * sizeof(float);
-    return launch<MODE_FWDM, KIND>(s, a, table_bytes(a), kd_dev, hdr_dev, nullptr, nullptr, nullptr, nullptr,
-                                   (hipStream_t)stream, tail, mat_dev, views_dev);
+    LaunchIO io;
+    io.kd = kd_dev, io.out = hdr_dev, io.mat = mat_dev, io.views = views_dev, io.stream = (hipStream_t)stream;
+    io.tail = (size_t)(kBlock / 64) * a.mean_wstride * sizeof(float);
+    return launch<MODE_FWDM, KIND>(s, a, table_bytes(a), io);
   }
   StreamScratch ws;
   if (ws.alloc((size_t)sets * npix * p.spp * 3 * sizeof(float), (hipStream_t)stream)) return -1;
@@ -2059,6 +2059,63 @@ int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev
   return render_mat_impl(s, p, kd_dev, ks_dev, ke_dev, hdr_dev, nullptr, stream);
 }
 
+// ------------------------------------------------------------ adjoints
+// The args of every adjoint launch: make_args, the image order of
+// IPT_ADJ_PIXEL_MAJOR, and the gradient bins (all triangles in LDS, or the
+// hot set of gpu_upload's grad_map).
+static TraceArgs adjoint_args(const GpuScene *s, const RenderParams &p) {
+  TraceArgs a = make_args(s, p);
+  a.sample_major = IPT_ADJ_PIXEL_MAJOR ? 0 : 1;  // (see IPT_ADJ_PIXEL_MAJOR)
+  if (s->grad_map) {
+    a.grad_slots = kLdsGradBytes / (3 * (int)sizeof(double));
+    a.grad_map = s->grad_map;
+    a.slot_tri = s->slot_tri;
+  } else {
+    a.grad_slots = s->host.nT;
+  }
+  return a;
+}
+
+// TraceArgs::rec_lds of an unbounded adjoint (kernel_of<MODE_ADJU, .., KIND>)
+// whose LDS is `base` bytes plus `per` bytes per ring slot: up to
+// IPT_ADJU_LDS_SLOTS (brute force) or IPT_ADJU_LDS_SLOTS_BVH slots, as many
+// as cost no resident workgroup (searched for the brute-force instances and
+// cached per scene for this base in *cached_base / *cached_nl; a variant
+// built with IPT_ADJU_LDS_SLOTS_FIXED >= 0 fixes the count, A/B timing); the
+// rest of the ring lives in global memory (launch_inst sizes that part).
+// At least 1: a lane's first record never waits for a pool chunk -- with none
+// left it could not start its ring -- so a scene whose base leaves no room
+// for one slot at full residency runs with one workgroup less; the callers
+// refuse one that leaves no room for one slot at all.
+template <int KIND>
+static int ring_lds_slots(GpuScene *s, size_t base, size_t per, bool bvh, size_t *cached_base, int *cached_nl,
+                          int *rec_lds) {
+  int nl = bvh ? IPT_ADJU_LDS_SLOTS_BVH : IPT_ADJU_LDS_SLOTS;
+  if (IPT_ADJU_LDS_SLOTS_FIXED >= 0) {
+    nl = IPT_ADJU_LDS_SLOTS_FIXED;
+  } else if (!bvh) {
+    if (*cached_base != base) {
+      auto occ = [&](size_t bytes, int *o) {
+        return s->has_ks ? hipOccupancyMaxActiveBlocksPerMultiprocessor(o, kernel_of<MODE_ADJU, true, false, KIND>(), kBlock, bytes)
+                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(o, kernel_of<MODE_ADJU, false, false, KIND>(), kBlock, bytes);
+      };
+      int occ0 = 0, best = 0;
+      HIP_TRY(occ(base, &occ0));
+      for (int k = nl; k > 0 && best == 0; --k) {
+        int o = 0;
+        HIP_TRY(occ(base + k * per, &o));
+        if (o >= occ0 && base + k * per <= IPT_ADJU_LDS_CAP) best = k;
+      }
+      *cached_base = base;
+      *cached_nl = best;
+    }
+    nl = *cached_nl;
+  }
+  if (g_adju_lds.load() > 0) nl = g_adju_lds.load();
+  *rec_lds = std::max(1, std::min(nl, kAdjuRing - 1));
+  return 0;
+}
+
 // dL/dKd, dL/dKs, dL/dKe in one launch of trace_mat_kernel (the bounded
 // adjoint only); grad_dev: 3 x nT x 3 doubles [Kd | Ks | Ke], accumulated.
 static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
@@ -2099,15 +2156,7 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
     gpu_set_error("adjoint supports at most 65535 triangles");
     return -1;
   }
-  TraceArgs a = make_args(s, p);
-  a.sample_major = IPT_ADJ_PIXEL_MAJOR ? 0 : 1;
-  if (s->grad_map) {
-    a.grad_slots = kLdsGradBytes / (3 * (int)sizeof(double));
-    a.grad_map = s->grad_map;
-    a.slot_tri = s->slot_tri;
-  } else {
-    a.grad_slots = s->host.nT;
-  }
+  const TraceArgs a = adjoint_args(s, p);
   const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
   // bins (Kd, Ks with a lobe, Ke per emitter) + tables + owner markers + vertex records
   const size_t lds = mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
@@ -2121,24 +2170,12 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
   const TriMat *mat = nullptr;
   if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
   if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
-  if (views_dev)
-    return launch<MODE_ADJ, KIND_VMAT>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr,
-                                       (hipStream_t)stream, 0, mat, views_dev);
-  return launch<MODE_ADJ, KIND_MATG>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream, 0,
-                                mat);
+  LaunchIO io;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.views = views_dev, io.stream = (hipStream_t)stream;
+  return views_dev ? launch<MODE_ADJ, KIND_VMAT>(s, a, lds, io) : launch<MODE_ADJ, KIND_MATG>(s, a, lds, io);
 }
 
 // ------------------------------------------------------------ views
-// camera_ray's origin M * (0,0,0,1) per row, with its own operations (fmaf is
-// the IEEE fma on host and device); make_args evaluates the same chain for
-// the scene's camera.
-static void camera_origin(const float *cam, float *org) {
-  for (int i = 0; i < 3; ++i) {
-    const float *M = cam + 4 * i;
-    org[i] = std::fmaf(M[3], 1.f, std::fmaf(M[2], 0.f, std::fmaf(M[1], 0.f, M[0] * 0.f)));
-  }
-}
-
 struct GpuViews {
   GpuScene *scene = nullptr;
   int n = 0;
@@ -2305,61 +2342,32 @@ int gpu_adjoint_mat_unbounded(GpuScene *s, const RenderParams &p, const float *k
     gpu_set_error("adjoint supports at most 65535 triangles");
     return -1;
   }
-  TraceArgs a = make_args(s, p);
-  a.sample_major = IPT_ADJ_PIXEL_MAJOR ? 0 : 1;
-  if (s->grad_map) {
-    a.grad_slots = kLdsGradBytes / (3 * (int)sizeof(double));
-    a.grad_map = s->grad_map;
-    a.slot_tri = s->slot_tri;
-  } else {
-    a.grad_slots = s->host.nT;
-  }
+  TraceArgs a = adjoint_args(s, p);
   const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
   const size_t per = fields * kBlock * sizeof(float);  // one ring slot per lane
   const bool bvh = use_bvh(s);
   // bins (Kd, Ks with a lobe, Ke per emitter) + tables + the owners' carried words + owner markers
   const size_t base = mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
                       mat_carry_bytes(bvh) + (size_t)kBlock * sizeof(uint32_t);
-  // ring slots in LDS, chosen as gpu_adjoint chooses them but for THIS
-  // kernel's occupancy and in a cache of its own (matu_base / matu_nl): the
-  // bins are larger than the Kd-only adjoint's, so the count may differ
-  a.rec_cap = kAdjuRing;
-  int nl = bvh ? IPT_ADJU_LDS_SLOTS_BVH : IPT_ADJU_LDS_SLOTS;
-  if (IPT_ADJU_LDS_SLOTS_FIXED >= 0) {
-    nl = IPT_ADJU_LDS_SLOTS_FIXED;
-  } else if (!bvh && base + per <= 160 * 1024) {
-    if (s->matu_base != base) {
-      auto occ = [&](size_t bytes, int *o) {
-        return s->has_ks ? hipOccupancyMaxActiveBlocksPerMultiprocessor(o, trace_matu_kernel<true, false>, kBlock, bytes)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(o, trace_matu_kernel<false, false>, kBlock, bytes);
-      };
-      int occ0 = 0, best = 0;
-      HIP_TRY(occ(base, &occ0));
-      for (int k = nl; k > 0 && best == 0; --k) {
-        int o = 0;
-        HIP_TRY(occ(base + k * per, &o));
-        if (o >= occ0 && base + k * per <= IPT_ADJU_LDS_CAP) best = k;
-      }
-      s->matu_base = base;
-      s->matu_nl = best;
-    }
-    nl = s->matu_nl;
-  }
-  if (g_adju_lds.load() > 0) nl = g_adju_lds.load();
-  a.rec_lds = std::max(1, std::min(nl, kAdjuRing - 1));  // (>= 1: see gpu_adjoint)
-  // a forced or default count the base leaves no room for shrinks to what fits
-  // (>= 1); a base with no room for one slot per lane is refused
+  // a base with no room for one slot per lane is refused
   if (base + per > 160 * 1024) {
     gpu_set_error("unbounded material adjoint: the Kd/Ks/Ke bins and the scene's LDS tables plus one record slot per lane exceed 160 KiB");
     return -1;
   }
+  // ring slots in LDS, chosen as gpu_adjoint chooses them but for THIS
+  // kernel's occupancy and in a cache of its own: the bins are larger than
+  // the Kd-only adjoint's, so the count may differ
+  a.rec_cap = kAdjuRing;
+  if (ring_lds_slots<KIND_MATG>(s, base, per, bvh, &s->matu_base, &s->matu_nl, &a.rec_lds)) return -1;
+  // a forced or default count the base leaves no room for shrinks to what fits (>= 1)
   a.rec_lds = (int)std::min<size_t>((size_t)a.rec_lds, (160 * 1024 - base) / per);
   const size_t lds = base + (size_t)a.rec_lds * per;
   StreamScratch tab;
   const TriMat *mat = nullptr;
   if (pack_materials(s, ks_dev, ke_dev, 1, (hipStream_t)stream, tab, &mat)) return -1;
-  return launch<MODE_ADJU, KIND_MATG>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream,
-                                      0, mat);
+  LaunchIO io;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.stream = (hipStream_t)stream;
+  return launch<MODE_ADJU, KIND_MATG>(s, a, lds, io);
 }
 
 // Bounded adjoint launches of at least this many samples (all material sets)
@@ -2379,76 +2387,32 @@ int gpu_adjoint(GpuScene *s, const RenderParams &p, const float *kd_dev, const f
     gpu_set_error("adjoint supports at most 65535 triangles");
     return -1;
   }
-  TraceArgs a = make_args(s, p);
-  a.sample_major = IPT_ADJ_PIXEL_MAJOR ? 0 : 1;  // (see IPT_ADJ_PIXEL_MAJOR)
-  if (s->grad_map) {
-    a.grad_slots = kLdsGradBytes / (3 * (int)sizeof(double));
-    a.grad_map = s->grad_map;
-    a.slot_tri = s->slot_tri;
-  } else {
-    a.grad_slots = s->host.nT;
-  }
+  TraceArgs a = adjoint_args(s, p);
   const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
+  const size_t per = fields * kBlock * sizeof(float);  // one vertex record (ADJU: ring slot) per lane
   const size_t base = (size_t)a.grad_slots * 3 * sizeof(double) + table_bytes(a) +
                       (size_t)kBlock * sizeof(uint32_t);  // + the sweep's owner markers
   if (unbounded) {
-    // ring slots in LDS: up to IPT_ADJU_LDS_SLOTS (brute force) or
-    // IPT_ADJU_LDS_SLOTS_BVH, as many as cost no resident workgroup (a
-    // variant built with IPT_ADJU_LDS_SLOTS_FIXED >= 0 fixes the count, A/B
-    // timing); the rest of the ring in global memory
     a.rec_cap = kAdjuRing;
-    const bool bvh = use_bvh(s);
-    int nl = bvh ? IPT_ADJU_LDS_SLOTS_BVH : IPT_ADJU_LDS_SLOTS;
-    if (IPT_ADJU_LDS_SLOTS_FIXED >= 0) {
-      nl = IPT_ADJU_LDS_SLOTS_FIXED;
-    } else if (!bvh) {
-      const size_t per = fields * kBlock * sizeof(float);
-      if (s->adju_base != base) {  // cached per scene for this LDS base
-        int occ0 = 0;
-        HIP_TRY(s->has_ks ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ0, trace_kernel<MODE_ADJU, true, false>,
-                                                                         kBlock, base)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ0, trace_kernel<MODE_ADJU, false, false>,
-                                                                         kBlock, base));
-        int best = 0;
-        for (int k = nl; k > 0 && best == 0; --k) {
-          int o = 0;
-          HIP_TRY(s->has_ks ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, trace_kernel<MODE_ADJU, true, false>,
-                                                                           kBlock, base + k * per)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, trace_kernel<MODE_ADJU, false, false>,
-                                                                           kBlock, base + k * per));
-          if (o >= occ0 && base + k * per <= IPT_ADJU_LDS_CAP) best = k;
-        }
-        s->adju_base = base;
-        s->adju_nl = best;
-      }
-      nl = s->adju_nl;
-    }
-    // (>= 1: a lane's first record never waits for a pool chunk -- with none
-    // left it could not start its ring -- so a scene whose LDS base leaves no
-    // room for one slot at full residency runs with one workgroup less; one
-    // that leaves no room for one slot at all is refused below; launch_inst
-    // sizes the global part)
-    if (g_adju_lds.load() > 0) nl = g_adju_lds.load();
-    a.rec_lds = std::max(1, std::min(nl, kAdjuRing - 1));
+    if (ring_lds_slots<KIND_TRACE>(s, base, per, use_bvh(s), &s->adju_base, &s->adju_nl, &a.rec_lds)) return -1;
   }
-  const size_t lds = base + (size_t)(unbounded ? a.rec_lds : a.rec_cap) * fields * kBlock * sizeof(float);
+  const size_t lds = base + (size_t)(unbounded ? a.rec_lds : a.rec_cap) * per;
   if (lds > 160 * 1024) {
     gpu_set_error(unbounded ? "unbounded adjoint: the scene's LDS tables plus one record slot per lane exceed 160 KiB"
                             : "adjoint LDS footprint exceeds 160 KiB; lower max_bounces");
     return -1;
   }
-  if (unbounded)
-    return launch<MODE_ADJU>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream);
+  LaunchIO io;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.stream = (hipStream_t)stream;
+  if (unbounded) return launch<MODE_ADJU>(s, a, lds, io);
   // the 6-wave instance for full-size launches whose LDS leaves room for a
   // sixth workgroup per CU (IPT_ADJW=0/1 in the environment forces the choice)
-  const size_t lane_words = IPT_ADJW_LANE_LDS ? (size_t)6 * kBlock * sizeof(uint32_t) : 0;  // trace_kernel's lane_ws
+  const size_t lane_words = IPT_ADJW_LANE_LDS ? kLaneWsBytes : 0;
   bool wide = !use_bvh(s) && !s->has_ks && 6 * (lds + lane_words) <= 160 * 1024 &&
               (uint64_t)a.n_samples * (uint64_t)std::max(1, a.nscenes) >= IPT_ADJW_MIN_SAMPLES;
   if (const char *e = std::getenv("IPT_ADJW")) wide = std::atoi(e) != 0 && !use_bvh(s) && !s->has_ks;
-  if (wide)
-    return launch<MODE_ADJW>(s, a, lds + lane_words, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr,
-                             (hipStream_t)stream);
-  return launch<MODE_ADJ>(s, a, lds, kd_dev, nullptr, adj_dev, grad_dev, nullptr, nullptr, (hipStream_t)stream);
+  if (wide) return launch<MODE_ADJW>(s, a, lds + lane_words, io);
+  return launch<MODE_ADJ>(s, a, lds, io);
 }
 
 int gpu_graph(GpuScene *s, const RenderParams &p, const uint8_t *target_dev, double *acc_dev, void *stream) {
@@ -2458,8 +2422,9 @@ int gpu_graph(GpuScene *s, const RenderParams &p, const uint8_t *target_dev, dou
   a.lds_edges = bins <= (size_t)IPT_GRAPH_LDS_KB * 1024 ? 1 : 0;
   a.kd_tables = 0;  // the graph integrator never reads albedo
   a.sample_major = IPT_GRAPH_PIXEL_MAJOR ? 0 : 1;  // (see IPT_ADJ_PIXEL_MAJOR)
-  return launch<MODE_GRAPH>(s, a, (a.lds_edges ? bins : 0) + table_bytes(a), nullptr, nullptr, nullptr, nullptr, target_dev, acc_dev,
-                            (hipStream_t)stream);
+  LaunchIO io;
+  io.target = target_dev, io.edges = acc_dev, io.stream = (hipStream_t)stream;
+  return launch<MODE_GRAPH>(s, a, (a.lds_edges ? bins : 0) + table_bytes(a), io);
 }
 
 // ------------------------------------------------------------ math self-test
@@ -2758,6 +2723,21 @@ struct DevBuf {
     if (p) (void)hipFree(p);
   }
 };
+
+// The round trip of the adjoint and graph wrappers: `in` (n_in elements)
+// uploaded, an accumulator of n_acc doubles zeroed, run(in_dev, acc_dev), the
+// accumulator downloaded.
+template <typename T, typename F>
+int accumulate_host(const T *in, size_t n_in, double *acc, size_t n_acc, F run) {
+  DevBuf i, a;
+  HIP_TRY(hipMalloc(&i.p, n_in * sizeof(T)));
+  HIP_TRY(hipMalloc(&a.p, n_acc * sizeof(double)));
+  HIP_TRY(hipMemcpy(i.p, in, n_in * sizeof(T), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(a.p, 0, n_acc * sizeof(double)));
+  if (run((const T *)i.p, (double *)a.p)) return -1;
+  HIP_TRY(hipMemcpy(acc, a.p, n_acc * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
 }  // namespace
 
 int gpu_render_samples_host(GpuScene *s, const RenderParams &p, float *samples) {
@@ -2785,40 +2765,25 @@ int gpu_render_host(GpuScene *s, const RenderParams &p, float *hdr, uint8_t *ldr
 int gpu_adjoint_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad) {
   if (check_params(s, p)) return -1;
   const size_t na = (size_t)p.width * p.height * 3, ng = (size_t)s->host.nT * 3;
-  DevBuf a, g;
-  HIP_TRY(hipMalloc(&a.p, na * sizeof(float)));
-  HIP_TRY(hipMalloc(&g.p, ng * sizeof(double)));
-  HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
-  if (gpu_adjoint(s, p, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
-  HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return accumulate_host(adj, na, grad, ng, [&](const float *a, double *g) {
+    return gpu_adjoint(s, p, nullptr, a, g, nullptr);
+  });
 }
 
 int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad) {
   if (check_params(s, p)) return -1;
   const size_t na = (size_t)p.width * p.height * 3, ng = (size_t)s->host.nT * 9;
-  DevBuf a, g;
-  HIP_TRY(hipMalloc(&a.p, na * sizeof(float)));
-  HIP_TRY(hipMalloc(&g.p, ng * sizeof(double)));
-  HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
-  if (gpu_adjoint_mat(s, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
-  HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return accumulate_host(adj, na, grad, ng, [&](const float *a, double *g) {
+    return gpu_adjoint_mat(s, p, nullptr, nullptr, nullptr, a, g, nullptr);
+  });
 }
 
 int gpu_adjoint_mat_unbounded_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad) {
   if (check_unbounded(p) || check_params(s, p)) return -1;
   const size_t na = (size_t)p.width * p.height * 3, ng = (size_t)s->host.nT * 9;
-  DevBuf a, g;
-  HIP_TRY(hipMalloc(&a.p, na * sizeof(float)));
-  HIP_TRY(hipMalloc(&g.p, ng * sizeof(double)));
-  HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
-  if (gpu_adjoint_mat_unbounded(s, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
-  HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return accumulate_host(adj, na, grad, ng, [&](const float *a, double *g) {
+    return gpu_adjoint_mat_unbounded(s, p, nullptr, nullptr, nullptr, a, g, nullptr);
+  });
 }
 
 int gpu_render_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, float *hdr) {
@@ -2836,14 +2801,9 @@ int gpu_adjoint_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p
   RenderParams q = p;
   if (views_adjoint_bounces(p) || views_params(s, v, q)) return -1;
   const size_t na = (size_t)v->n * p.width * p.height * 3, ng = (size_t)s->host.nT * 9;
-  DevBuf a, g;
-  HIP_TRY(hipMalloc(&a.p, na * sizeof(float)));
-  HIP_TRY(hipMalloc(&g.p, ng * sizeof(double)));
-  HIP_TRY(hipMemcpy(a.p, adj, na * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(g.p, 0, ng * sizeof(double)));
-  if (gpu_adjoint_views(s, v, p, nullptr, nullptr, nullptr, (const float *)a.p, (double *)g.p, nullptr)) return -1;
-  HIP_TRY(hipMemcpy(grad, g.p, ng * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return accumulate_host(adj, na, grad, ng, [&](const float *a, double *g) {
+    return gpu_adjoint_views(s, v, p, nullptr, nullptr, nullptr, a, g, nullptr);
+  });
 }
 
 int gpu_closest_hit_host(GpuScene *s, int64_t n, const float *org, const float *dir, const int *targets,
@@ -2877,14 +2837,7 @@ int gpu_graph_host(GpuScene *s, const RenderParams &p, const uint8_t *target, do
   if (check_params(s, p)) return -1;
   const size_t nt = (size_t)p.width * p.height * 3;
   const size_t nb = (size_t)(s->host.nT + 1) * s->host.nT * kEdgeW;
-  DevBuf t, e;
-  HIP_TRY(hipMalloc(&t.p, nt));
-  HIP_TRY(hipMalloc(&e.p, nb * sizeof(double)));
-  HIP_TRY(hipMemcpy(t.p, target, nt, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(e.p, 0, nb * sizeof(double)));
-  if (gpu_graph(s, p, (const uint8_t *)t.p, (double *)e.p, nullptr)) return -1;
-  HIP_TRY(hipMemcpy(acc, e.p, nb * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  return accumulate_host(target, nt, acc, nb, [&](const uint8_t *t, double *e) { return gpu_graph(s, p, t, e, nullptr); });
 }
 
 }  // namespace ipt
