@@ -319,6 +319,23 @@ int ipt_render_views_dev(void *scene, void *views, const ipt_params_t *p, uint64
 int ipt_adjoint_views_dev(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, const float *kd_dev,
                           const float *ks_dev, const float *ke_dev, const float *adj_dev, double *grad_dev,
                           void *stream);
+/* Views x material sets: ONE launch traces n_sets material
+ * sets through all V views.  kd_dev / ks_dev / ke_dev: n_sets*nT*3 device
+ * floats (NULL = the scene's own values in every set).  Pair (s, b) uses seed
+ * p->seed + (s*V + b)*seed_stride and equals view b of ipt_render_views_dev
+ * with set s's arrays at that seed, bit for bit.  grad_dev: one [Kd | Ks | Ke]
+ * block of 3*nT*3 doubles per set, ACCUMULATED over the set's views (zero it
+ * first).  Bounded estimator only, for the pair: max_bounces 0..62.  Refused
+ * with a message before anything is enqueued: n_sets < 1, n_sets*V > 65535,
+ * max_bounces outside 0..62, more than 65535 triangles, a views handle of
+ * another scene (or one not live), an LDS footprint above 160 KiB. */
+int ipt_render_views_batch_dev(void *scene, void *views, const ipt_params_t *p, int n_sets, uint64_t seed_stride,
+                               const float *kd_dev, const float *ks_dev, const float *ke_dev, /* n_sets*nT*3 or NULL */
+                               float *hdr_dev /* [n_sets][V][rows][W][3] */, void *stream);
+int ipt_adjoint_views_batch_dev(void *scene, void *views, const ipt_params_t *p, int n_sets, uint64_t seed_stride,
+                                const float *kd_dev, const float *ks_dev, const float *ke_dev,
+                                const float *adj_dev /* [n_sets][V][H][W][3], full frames */,
+                                double *grad_dev /* [n_sets][Kd|Ks|Ke][nT][3], accumulated */, void *stream);
 /* Host-memory forms with the scene's own materials (synchronous). */
 int ipt_render_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride,
                           float *hdr /*V*rows*W*3*/);

@@ -120,6 +120,8 @@ SIGNATURES = {
     "ipt_views_count": (C.c_int, [vp]),
     "ipt_render_views_dev": (C.c_int, [vp, vp, pp, C.c_uint64, vp, vp, vp, vp, vp]),
     "ipt_adjoint_views_dev": (C.c_int, [vp, vp, pp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "ipt_render_views_batch_dev": (C.c_int, [vp, vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp]),
+    "ipt_adjoint_views_batch_dev": (C.c_int, [vp, vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "ipt_render_views_host": (C.c_int, [vp, vp, pp, C.c_uint64, fp]),
     "ipt_adjoint_views_host": (C.c_int, [vp, vp, pp, C.c_uint64, fp, dp]),
     "ipt_views_rays_host": (C.c_int, [vp, vp, C.c_int, pp, C.c_int64, C.POINTER(C.c_int64), fp, fp]),

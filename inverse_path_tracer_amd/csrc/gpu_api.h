@@ -80,6 +80,14 @@ int gpu_render_views(GpuScene *s, const GpuViews *v, RenderParams p, const float
                      const float *ke_dev, float *hdr_dev, void *stream);
 int gpu_adjoint_views(GpuScene *s, const GpuViews *v, RenderParams p, const float *kd_dev, const float *ks_dev,
                       const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
+// Views x material sets: n_sets material sets (kd / ks / ke n_sets*nT*3, nullptr = the scene's
+// own in every set) through every view in one launch; pair (m, b) traces seed + (m*V + b)*seed_stride; hdr_dev
+// [n_sets][V] images, grad_dev one [Kd | Ks | Ke] block per set, accumulated.  Bounded (max_bounces 0..62) for both.
+int gpu_render_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                           const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream);
+int gpu_adjoint_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                            const float *ks_dev, const float *ke_dev, const float *adj_dev, double *grad_dev,
+                            void *stream);
 int gpu_render_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, float *hdr);
 int gpu_adjoint_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, const float *adj, double *grad);
 // The camera rays of view `view` for n global sample indices (host arrays; diagnostic).

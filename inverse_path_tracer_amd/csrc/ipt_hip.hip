@@ -811,6 +811,7 @@ __global__ IPT_TRACE_BOUNDS void trace_kernel(
   constexpr bool MATG = false;
   constexpr bool MATB = false;
   constexpr bool VIEWS = false;
+  constexpr bool VSETS = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -832,6 +833,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_mat_kernel(
   constexpr bool MATG = false;
   constexpr bool MATB = true;
   constexpr bool VIEWS = false;
+  constexpr bool VSETS = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -853,6 +855,7 @@ trace_mat_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const Tr
   constexpr bool MATG = true;
   constexpr bool MATB = false;
   constexpr bool VIEWS = false;
+  constexpr bool VSETS = false;
 #include "trace_body.h"
 }
 
@@ -874,6 +877,7 @@ trace_matu_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const T
   constexpr bool MATG = true;
   constexpr bool MATB = false;
   constexpr bool VIEWS = false;
+  constexpr bool VSETS = false;
 #include "trace_body.h"
 }
 
@@ -897,6 +901,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_views_kernel(
   constexpr bool MATG = false;
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
+  constexpr bool VSETS = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -914,6 +919,49 @@ trace_mat_views_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, co
   constexpr bool MATG = true;
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
+  constexpr bool VSETS = false;
+#include "trace_body.h"
+}
+
+// Views x material sets: the views' grid split over S * V
+// (set, view) pairs.  Launch set i traces material set i / V through camera
+// i % V: seed, image, adjoint image, grab counter and bps go by i as in every
+// batch, kd, mat, kd/pi and the gradient slice by i / V, the camera by i % V.
+// V follows the views' table as one more TRAILING parameter (TraceArgs keeps
+// its layout).  __global__s of their own, so the view kernels stay what they
+// were.
+template <int MODE, bool SPEC, bool BVH>
+__global__ IPT_TRACE_BOUNDS void trace_fwd_views_batch_kernel(
+    const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+    const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat, const float *__restrict__ kd,
+    const int *__restrict__ emit_tri, const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+    float *__restrict__ out_samples, const float *__restrict__ adj, double *__restrict__ grad,
+    const uint8_t *__restrict__ target, double *__restrict__ edges, const float *__restrict__ views,
+    const int nviews) {
+  static_assert(is_fwd<MODE>(), "forward instances only");
+  constexpr bool MATG = false;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = true;
+  constexpr bool VSETS = true;
+  const int *const tri_emit = nullptr;
+#include "trace_body.h"
+}
+template <bool SPEC, bool BVH>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
+                          amdgpu_waves_per_eu(min_blocks<MODE_ADJ, BVH>()))) void
+trace_mat_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+                             const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat,
+                             const float *__restrict__ kd, const int *__restrict__ emit_tri,
+                             const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+                             float *__restrict__ out_samples, const float *__restrict__ adj,
+                             double *__restrict__ grad, const uint8_t *__restrict__ target,
+                             double *__restrict__ edges, const int *__restrict__ tri_emit,
+                             const float *__restrict__ views, const int nviews) {
+  constexpr int MODE = MODE_ADJ;
+  constexpr bool MATG = true;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = true;
+  constexpr bool VSETS = true;
 #include "trace_body.h"
 }
 
@@ -1070,24 +1118,32 @@ static std::vector<double> pmf_reciprocals(const std::vector<float> &pmf) {
 // per-set tables trace_fwd_mat_kernel<MODE, SPEC, BVH>.
 // KIND_VFWD / KIND_VMAT: the views' forward and bounded material adjoint
 // (trace_fwd_views_kernel, trace_mat_views_kernel).
-enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4 };
-constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }
+// KIND_VBFWD / KIND_VBMAT: the same over (material set, view) pairs
+// (trace_fwd_views_batch_kernel, trace_mat_views_batch_kernel).
+enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4, KIND_VBFWD = 5, KIND_VBMAT = 6 };
+constexpr int kKindLast = KIND_VBMAT;
+constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }  // ONE material set
+constexpr bool kind_view_sets(int kind) { return kind == KIND_VBFWD || kind == KIND_VBMAT; }
 // The (MODE, KIND) pairs that have kernels (kernel_of's static_asserts).
 constexpr bool inst_valid(int mode, int kind) {
   return kind == KIND_TRACE  ? mode >= MODE_FWD && mode <= MODE_ADJW
          : kind == KIND_MATG ? mode == MODE_ADJ || mode == MODE_ADJU
-         : kind == KIND_VMAT ? mode == MODE_ADJ
+         : kind == KIND_VMAT || kind == KIND_VBMAT ? mode == MODE_ADJ
                              : mode == MODE_FWD || mode == MODE_FWDM;
 }
 // An instance's slot in GpuScene::inst.  0..23: trace_kernel<mode, spec, bvh>;
 // 24..27: trace_mat_kernel<spec, bvh>; 28..35: trace_fwd_mat_kernel<FWD | FWDM,
 // spec, bvh>; 36..39: trace_matu_kernel<spec, bvh>; 40..47:
-// trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh>.
+// trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh>;
+// 52..59: trace_fwd_views_batch_kernel<FWD | FWDM, spec, bvh>; 60..63:
+// trace_mat_views_batch_kernel<spec, bvh>.
 constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
   return (kind == KIND_MATG   ? (mode == MODE_ADJU ? 36 : 24)
           : kind == KIND_FWDB ? 28 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VFWD ? 40 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VMAT ? 48
+          : kind == KIND_VBFWD ? 52 + (mode == MODE_FWDM ? 4 : 0)
+          : kind == KIND_VBMAT ? 60
                               : mode * 4) +
          (spec ? 2 : 0) + (bvh ? 1 : 0);
 }
@@ -1095,7 +1151,7 @@ constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
 constexpr int inst_slot_count() {
   uint64_t seen = 0;
   int n = 0;
-  for (int kind = KIND_TRACE; kind <= KIND_VMAT; ++kind)
+  for (int kind = KIND_TRACE; kind <= kKindLast; ++kind)
     for (int mode = MODE_FWD; mode <= MODE_ADJW; ++mode)
       for (int sb = 0; sb < 4 && inst_valid(mode, kind); ++sb) {
         const int slot = inst_slot(mode, (sb & 2) != 0, (sb & 1) != 0, kind);
@@ -1363,7 +1419,13 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 // Occupancy queries and the launch itself go through it.
 template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr auto kernel_of() {
-  if constexpr (KIND == KIND_VMAT) {
+  if constexpr (KIND == KIND_VBMAT) {
+    static_assert(MODE == MODE_ADJ, "the view sets' adjoint is the bounded material adjoint");
+    return &trace_mat_views_batch_kernel<SPEC, BVH>;
+  } else if constexpr (KIND == KIND_VBFWD) {
+    static_assert(is_fwd<MODE>(), "the view sets' forward: forward instances only");
+    return &trace_fwd_views_batch_kernel<MODE, SPEC, BVH>;
+  } else if constexpr (KIND == KIND_VMAT) {
     static_assert(MODE == MODE_ADJ, "the views' adjoint is the bounded material adjoint");
     return &trace_mat_views_kernel<SPEC, BVH>;
   } else if constexpr (KIND == KIND_VFWD) {
@@ -1382,7 +1444,9 @@ constexpr auto kernel_of() {
 }
 // ... and its name, for the IPT_DEBUG_GRID prints.
 constexpr const char *kernel_name(int mode, int kind) {
-  return kind == KIND_VFWD   ? "trace_fwd_views_kernel"
+  return kind == KIND_VBFWD  ? "trace_fwd_views_batch_kernel"
+         : kind == KIND_VBMAT ? "trace_mat_views_batch_kernel"
+         : kind == KIND_VFWD ? "trace_fwd_views_kernel"
          : kind == KIND_VMAT ? "trace_mat_views_kernel"
          : kind == KIND_MATG ? (mode == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
          : kind == KIND_FWDB ? "trace_fwd_mat_kernel"
@@ -1629,6 +1693,7 @@ struct LaunchIO {
   double *edges = nullptr;          // ... and bins
   const TriMat *mat = nullptr;  // TriMat table (nullptr: the scene's own; the overrides pass what pack_mat_kernel wrote)
   const float *views = nullptr;  // KIND_VFWD / KIND_VMAT: the views' table
+  int nviews = 0;                // KIND_VBFWD / KIND_VBMAT: its entries V (the launch has nscenes / V material sets)
   hipStream_t stream = nullptr;
   size_t tail = 0;  // bytes per workgroup behind everything else (16-B aligned; the fused pixel mean's slots, TraceArgs::mean_off)
 };
@@ -1723,7 +1788,9 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const Launch
                        s->geom, io.mat ? io.mat : s->mat, io.kd ? io.kd : s->kd, s->emit_tri, s->emit_cdf, s->emit_pmf,
                        io.out, io.adj, io.grad, io.target, io.edges, trailing...);
   };
-  if constexpr (KIND == KIND_VMAT) enqueue(s->tri_emit, io.views);
+  if constexpr (KIND == KIND_VBMAT) enqueue(s->tri_emit, io.views, io.nviews);
+  else if constexpr (KIND == KIND_VBFWD) enqueue(io.views, io.nviews);
+  else if constexpr (KIND == KIND_VMAT) enqueue(s->tri_emit, io.views);
   else if constexpr (KIND == KIND_VFWD) enqueue(io.views);
   else if constexpr (KIND == KIND_MATG) enqueue(s->tri_emit);
   else enqueue();
@@ -1786,14 +1853,15 @@ static int launch(GpuScene *s, TraceArgs a, size_t lds, const LaunchIO &io) {
   const hipStream_t st = io.stream;
   // a batch's per-launch table holds one TriMat table per set (pack_materials);
   // its forward runs the instances that offset mat per set
-  // (views: one table, one kd for every set)
-  a.mat_stride = (io.mat && a.nscenes > 1 && !kind_views(KIND)) ? (uint32_t)a.nT : 0u;
+  // (views: one table, one kd for every set; view sets: one of each per material set)
+  const int msets = kind_views(KIND) ? 1 : kind_view_sets(KIND) ? a.nscenes / io.nviews : a.nscenes;
+  a.mat_stride = (io.mat && msets > 1) ? (uint32_t)a.nT : 0u;
   if constexpr (is_fwd<MODE>() && KIND == KIND_TRACE) {
     if (a.mat_stride) return launch<MODE, KIND_FWDB>(s, a, lds, io);
   }
   StreamScratch kdpi;
   if (MODE != MODE_GRAPH && !a.kd_tables && a.n_samples > 0) {
-    const int n = 3 * s->host.nT * (kind_views(KIND) ? 1 : a.nscenes);
+    const int n = 3 * s->host.nT * msets;
     if (kdpi.alloc((size_t)n * sizeof(float), st)) return -1;
     hipLaunchKernelGGL(kdpi_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, io.kd ? io.kd : s->kd, n,
                        (float *)kdpi.p);
@@ -1837,12 +1905,14 @@ int gpu_pixel_mean(const float *samples_dev, int64_t npix, int spp, float *hdr_d
 
 template <int KIND = KIND_TRACE>
 static int render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev,
-                             void *stream, const TriMat *mat_dev, const float *views_dev = nullptr) {
+                             void *stream, const TriMat *mat_dev, const float *views_dev = nullptr,
+                             int nviews = 0) {
   if (check_params(s, p)) return -1;
   TraceArgs a = make_args(s, p);
   a.sample_major = 1;
   LaunchIO io;
-  io.kd = kd_dev, io.out = samples_dev, io.mat = mat_dev, io.views = views_dev, io.stream = (hipStream_t)stream;
+  io.kd = kd_dev, io.out = samples_dev, io.mat = mat_dev, io.views = views_dev, io.nviews = nviews;
+  io.stream = (hipStream_t)stream;
   return launch<MODE_FWD, KIND>(s, a, table_bytes(a), io);
 }
 int gpu_render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev,
@@ -1925,9 +1995,10 @@ static FusedShape fused_shape(const RenderParams &p, bool bvh) {
 
 // mat_dev: the launch's TriMat table (nullptr: the scene's own)
 // KIND_VFWD: the sets are the views of views_dev (gpu_render_views)
+// KIND_VBFWD: the sets are (material set, view) pairs over its nviews entries (gpu_render_views_batch)
 template <int KIND = KIND_TRACE>
 static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, float *hdr_dev, uint8_t *ldr_dev,
-                       void *stream, const TriMat *mat_dev, const float *views_dev = nullptr) {
+                       void *stream, const TriMat *mat_dev, const float *views_dev = nullptr, int nviews = 0) {
   if (check_params(s, p)) return -1;
   const int64_t npix = (int64_t)band_rows(p) * p.width;
   const int sets = p.nscenes > 1 ? p.nscenes : 1;
@@ -1945,13 +2016,14 @@ static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, 
     a.ldr = ldr_dev;
     a.out_stride = (uint64_t)npix * 3;  // per material set: its own HDR (and LDR) image
     LaunchIO io;
-    io.kd = kd_dev, io.out = hdr_dev, io.mat = mat_dev, io.views = views_dev, io.stream = (hipStream_t)stream;
+    io.kd = kd_dev, io.out = hdr_dev, io.mat = mat_dev, io.views = views_dev, io.nviews = nviews;
+    io.stream = (hipStream_t)stream;
     io.tail = (size_t)(kBlock / 64) * a.mean_wstride * sizeof(float);
     return launch<MODE_FWDM, KIND>(s, a, table_bytes(a), io);
   }
   StreamScratch ws;
   if (ws.alloc((size_t)sets * npix * p.spp * 3 * sizeof(float), (hipStream_t)stream)) return -1;
-  if (render_samples_sm<KIND>(s, p, kd_dev, (float *)ws.p, stream, mat_dev, views_dev)) return -1;
+  if (render_samples_sm<KIND>(s, p, kd_dev, (float *)ws.p, stream, mat_dev, views_dev, nviews)) return -1;
   return pixel_mean_sm_sets((const float *)ws.p, npix, p.spp, sets, hdr_dev, ldr_dev, stream);
 }
 int gpu_render(GpuScene *s, const RenderParams &p, const float *kd_dev, float *hdr_dev, uint8_t *ldr_dev,
@@ -2116,11 +2188,19 @@ static int ring_lds_slots(GpuScene *s, size_t base, size_t per, bool bvh, size_t
   return 0;
 }
 
+// LDS bytes of a bounded material adjoint's workgroup: bins (Kd, Ks with a
+// lobe, Ke per emitter) + tables + owner markers + vertex records
+static size_t mat_adjoint_lds(const GpuScene *s, const TraceArgs &a) {
+  const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
+  return mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
+         (size_t)kBlock * sizeof(uint32_t) + (size_t)a.rec_cap * fields * kBlock * sizeof(float);
+}
+
 // dL/dKd, dL/dKs, dL/dKe in one launch of trace_mat_kernel (the bounded
 // adjoint only); grad_dev: 3 x nT x 3 doubles [Kd | Ks | Ke], accumulated.
 static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
                             const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream,
-                            const float *views_dev = nullptr);
+                            const float *views_dev = nullptr, int view_sets = 0);
 int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
                     const float *adj_dev, double *grad_dev, void *stream) {
   if (check_params(s, p)) return -1;
@@ -2140,10 +2220,12 @@ int gpu_adjoint_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_de
   return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream);
 }
 
-// views_dev: the sets are views over ONE material set and one gradient (gpu_adjoint_views)
+// views_dev: the sets are views over ONE material set and one gradient (gpu_adjoint_views),
+// or with view_sets > 0 the (material set, view) pairs of view_sets material
+// sets and as many gradients (gpu_adjoint_views_batch)
 static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
                             const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream,
-                            const float *views_dev) {
+                            const float *views_dev, int view_sets) {
   if (p.max_bounces < 0) {
     gpu_set_error("material adjoint: the unbounded estimator (max_bounces < 0) is not supported here; give max_bounces in 0..62, or call ipt_adjoint_mat_unbounded_dev (one material set)");
     return -1;
@@ -2157,21 +2239,22 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
     return -1;
   }
   const TraceArgs a = adjoint_args(s, p);
-  const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
-  // bins (Kd, Ks with a lobe, Ke per emitter) + tables + owner markers + vertex records
-  const size_t lds = mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
-                     (size_t)kBlock * sizeof(uint32_t) + (size_t)a.rec_cap * fields * kBlock * sizeof(float);
+  const size_t lds = mat_adjoint_lds(s, a);
   if (lds > 160 * 1024) {
     gpu_set_error("material adjoint: LDS footprint (Kd/Ks/Ke bins + tables + vertex records) exceeds 160 KiB; lower max_bounces");
     return -1;
   }
-  const int sets = (p.nscenes > 1 && !views_dev) ? p.nscenes : 1;
+  const int sets = view_sets > 0 ? view_sets : (p.nscenes > 1 && !views_dev) ? p.nscenes : 1;
   StreamScratch tab, kdrep;
   const TriMat *mat = nullptr;
   if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
   if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
   LaunchIO io;
   io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.views = views_dev, io.stream = (hipStream_t)stream;
+  if (view_sets > 0) {
+    io.nviews = p.nscenes / view_sets;
+    return launch<MODE_ADJ, KIND_VBMAT>(s, a, lds, io);
+  }
   return views_dev ? launch<MODE_ADJ, KIND_VMAT>(s, a, lds, io) : launch<MODE_ADJ, KIND_MATG>(s, a, lds, io);
 }
 
@@ -2281,6 +2364,64 @@ int gpu_adjoint_views(GpuScene *s, const GpuViews *v, RenderParams p, const floa
                       const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
   if (views_adjoint_bounces(p) || views_params(s, v, p)) return -1;
   return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream, v->dev);
+}
+
+// ------------------------------------------------------------ views x material sets
+// What both entry points refuse before anything is enqueued -- the argument
+// checks first, so a host-only scene reports them too; the forward's bounce
+// limit is the adjoint's (one contract for the pair, like the material batch).
+static int view_sets_params(GpuScene *s, const GpuViews *v, RenderParams &p, int n_sets) {
+  if (n_sets < 1) {
+    gpu_set_error("views batch: n_sets must be >= 1");
+    return -1;
+  }
+  if ((int64_t)n_sets * v->n > 65535) {
+    gpu_set_error("views batch: at most 65535 (material set, view) pairs per launch (n_sets * n_views)");
+    return -1;
+  }
+  if (p.max_bounces < 0 || p.max_bounces > kMaxAdjBounces) {
+    gpu_set_error("views batch: give max_bounces in 0..62 (the unbounded estimator is not supported)");
+    return -1;
+  }
+  if (s->host.nT > kMaxAdjTris) {
+    gpu_set_error("views batch supports at most 65535 triangles");
+    return -1;
+  }
+  if (v->scene != s) {
+    gpu_set_error("views: the handle was created for another scene");
+    return -1;
+  }
+  p.nscenes = n_sets * v->n;
+  return check_params(s, p);
+}
+
+// One launch renders n_sets material sets through every view: kd / ks / ke
+// are n_sets*nT*3 device arrays (nullptr: the scene's own values in every
+// set), hdr_dev [n_sets][V] images.  Pair (m, b) is gpu_render_views' view b
+// of set m's arrays at seed + (m * V + b) * seed_stride, bit for bit.
+int gpu_render_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                           const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream) {
+  if (view_sets_params(s, v, p, n_sets)) return -1;
+  // (the adjoint's LDS limit holds for the pair: refuse here what it would refuse)
+  if (mat_adjoint_lds(s, adjoint_args(s, p)) > 160 * 1024) {
+    gpu_set_error("views batch: LDS footprint (Kd/Ks/Ke bins + tables + vertex records) exceeds 160 KiB; lower max_bounces");
+    return -1;
+  }
+  StreamScratch tab, kdrep;  // freed behind the launch, in stream order
+  const TriMat *mat = nullptr;
+  if (batch_kd(s, &kd_dev, n_sets, (hipStream_t)stream, kdrep)) return -1;
+  if (pack_materials(s, ks_dev, ke_dev, n_sets, (hipStream_t)stream, tab, &mat)) return -1;
+  return render_impl<KIND_VBFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, mat, v->dev, v->n);
+}
+
+// grad_dev: n_sets x 3 x nT x 3 doubles [set][Kd | Ks | Ke][tri][c],
+// accumulated: the V * bps workgroups of a material set flush into its slice.
+// adj_dev: [n_sets][V] full frames.
+int gpu_adjoint_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                            const float *ks_dev, const float *ke_dev, const float *adj_dev, double *grad_dev,
+                            void *stream) {
+  if (view_sets_params(s, v, p, n_sets)) return -1;
+  return adjoint_mat_impl(s, p, kd_dev, ks_dev, ke_dev, adj_dev, grad_dev, stream, v->dev, n_sets);
 }
 
 // The rays of view `view` for n global sample indices (host arrays).

@@ -11,7 +11,9 @@
 // TraceKernArgs under their names, and tri_emit (MATG: triangle -> emitter
 // index or -1; nullptr otherwise), and VIEWS (the sets of the grid split are
 // cameras over one material set, DESIGN.md §18: the view kernels' trailing
-// parameter is the views' table, read by its kernarg offset).
+// parameter is the views' table, read by its kernarg offset), and VSETS (with
+// VIEWS: the sets are (material set, view) pairs, DESIGN.md §20 -- the view
+// count V follows the table as one more trailing parameter).
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   // scene batch: this workgroup's material set and its place among the set's blocks
@@ -19,18 +21,30 @@
   const uint32_t sblock = a.nscenes > 1 ? blockIdx.x / (uint32_t)a.nscenes : blockIdx.x;
   const uint32_t sgrid = a.nscenes > 1 ? (uint32_t)a.bps : gridDim.x;
   const uint64_t seed = a.seed + (uint64_t)set * a.seed_stride;
+  // VSETS: launch set `set` of S * V is material set set / V seen through view
+  // set % V (wave-uniform, once per workgroup).  Seed, image, adjoint image,
+  // grab counter and bps stay keyed by `set`; kd, mat, kd/pi and the gradient
+  // go by mset, the camera by view.
+  int mset = 0, view = set;
+  if (VSETS) {
+    const int nviews = karg<int>(sizeof(TraceKernArgs) + (MATG ? sizeof(void *) : 0) + sizeof(const float *));
+    mset = set / nviews;
+    view = set - mset * nviews;
+  }
   if (a.nscenes > 1) {
     // (VIEWS: the sets are views of ONE material set -- kd, mat, kd/pi and the
     // gradient carry no per-set offset)
     if (!VIEWS) kd += (size_t)set * 3 * a.nT;
+    else if (VSETS) kd += (size_t)mset * 3 * a.nT;
     // per-set TriMat tables (0: one table for every set): the material
     // adjoint, and the forward instances of the material overrides' batch
     if (!VIEWS && (MATG || MATB)) mat += (size_t)set * a.mat_stride;
+    else if (VSETS) mat += (size_t)mset * a.mat_stride;
     if (is_fwd<MODE>()) out_samples += (size_t)set * a.out_stride;
     // (adj, grad: karg() at their uses, offset there; a set's gradient is
     // 3 nT doubles, or with MATG its [Kd | Ks | Ke] slice of 9 nT)
   }
-  const float *kdpi_g = a.kdpi_g ? a.kdpi_g + (VIEWS ? (size_t)0 : (size_t)set * 3 * a.nT) : nullptr;
+  const float *kdpi_g = a.kdpi_g ? a.kdpi_g + (VIEWS ? (VSETS ? (size_t)mset * 3 * a.nT : (size_t)0) : (size_t)set * 3 * a.nT) : nullptr;
   constexpr int nthr = kBlock;
   const int nT = a.nT, nE = a.nE;
   const int vmax = a.rec_cap;  // ADJ record capacity per lane (ADJU: ring slots)
@@ -444,7 +458,7 @@
       // -- scalar loads from the scalar cache, taken again every iteration
       // instead of 19 SGPRs held through the loop.
       const cst_f32 *vq = (const cst_f32 *)karg<const float *>(sizeof(TraceKernArgs) + (MATG ? sizeof(void *) : 0)) +
-                          (size_t)set * kViewFloats;
+                          (size_t)view * kViewFloats;
       asm volatile("" : "+s"(vq));
 #pragma unroll
       for (int i = 0; i < 16; ++i) a.cam[i] = vq[i];
@@ -1338,7 +1352,7 @@
             }
             const int sl = a.grad_map ? a.grad_map[tk] : tk;
             const double v[3] = {(double)(ax * gk.x), (double)(ay * gk.y), (double)(az * gk.z)};
-            double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (!VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0);
+            double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (VSETS ? (size_t)mset * 9 * a.nT : !VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0);
             bins_add(sl >= 0, grad, sl >= 0 ? (size_t)sl * 3 : (size_t)tk * 3, 3, v);
             if (MATG) {  // dL/dKs[tk], dL/dKe[et_k], dL/dKe[tri_0] (global layout [Kd | Ks | Ke], nT*3 each)
               const size_t gs3 = (size_t)a.grad_slots * 3;
@@ -1428,7 +1442,7 @@
   if (!is_fwd<MODE>()) {
     __syncthreads();
     if (n_acc > 0) {
-      double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (!VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0)
+      double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (VSETS ? (size_t)mset * 9 * a.nT : !VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0)
                                     : edges;
       const int nb5 = (nT + 1) * nT * kEdgeL;
       for (int i = tid; i < n_acc; i += nthr) {

@@ -33,6 +33,11 @@ the ground-truth Kd with many more samples).
   adjoint launch per batch and step, over scenes that share geometry, emitter
   list, lobe flags and exponents and differ only in the values of Kd, Ks, Ke.
   The default, ``learn=("kd",)``, is the Kd-only path above, unchanged.
+* Views: ``build_tasks(views=cams)`` / ``MaterialOptimizer(views=cams)`` with
+  cams (V, 4, 4) observe every scene through V caller-supplied cameras
+  (DESIGN.md §20): targets are (V, H, W, 3), a step is still one forward and
+  one adjoint launch per batch (torch_ops.render_views_batch, S sets x V
+  views), for every ``learn``.  Without ``views`` nothing changes.
 
     python -m inverse_path_tracer_amd.optimize --scenes assets/scenes --n 13 --steps 200
 """
@@ -49,7 +54,7 @@ import torch
 
 from . import torch_ops
 from .distributed import allreduce_, world
-from .scene import Scene
+from .scene import Scene, Views
 
 # ipt_scene_export_triangles columns holding the diffuse Kd (everything else
 # is geometry / other material fields that must agree for a batch)
@@ -74,6 +79,7 @@ class SceneTask:
     ke: Optional[torch.Tensor] = None
     truth_ks: Optional[torch.Tensor] = None
     truth_ke: Optional[torch.Tensor] = None
+    views: Optional[Views] = None  # build_tasks(views=...): the cameras over `scene`; target is then (V, H, W, 3)
 
 
 def _scene_files(root: str, n: int) -> List[str]:
@@ -115,9 +121,17 @@ def _geometry_key(sc: Scene, materials: bool = False) -> bytes:
     return np.concatenate(parts, axis=1).tobytes()
 
 
+def _view_cams(views) -> np.ndarray:
+    cams = np.ascontiguousarray(np.asarray(views, np.float32))
+    if cams.ndim != 3 or cams.shape[0] < 1 or cams.shape[1:] != (4, 4):
+        raise ValueError("views must be (V, 4, 4) camera matrices, got %s" % (cams.shape,))
+    return cams
+
+
 def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_bounces: int, init: float,
                 device: torch.device, seed: int = 7, target_chunk: int = 16, first_index: int = 0,
-                learn: Sequence[str] = ("kd",), init_ks: float = 0.5, init_ke: float = 5.0) -> List[SceneTask]:
+                learn: Sequence[str] = ("kd",), init_ks: float = 0.5, init_ke: float = 5.0,
+                views=None) -> List[SceneTask]:
     """Load the scenes (one device geometry per distinct geometry), render the
     targets in batches of `target_chunk`, and create the parameters.  files[i]
     is global scene first_index + i: its target render traces the samples of
@@ -127,21 +141,31 @@ def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_
     the values of Kd, Ks, Ke share one geometry handle; the tasks carry ks, ke
     and their truths, the learned blocks start at init / init_ks / init_ke on
     the rows they act on (lobe rows, emitter rows) and the others at the truth;
-    the targets are rendered with the true values of all three."""
+    the targets are rendered with the true values of all three.
+
+    views, (V, 4, 4) camera matrices: one Views handle per geometry handle
+    (the tasks' ``views``), targets (V, H, W, 3) rendered with the truth through
+    torch_ops.render_views_batch -- scene i view b traces seed + 10^9 +
+    (i * V + b) * W*H*target_spp."""
+    cams = None if views is None else _view_cams(views)
     if set(learn) - set(_BLOCKS) or not tuple(learn):
         raise ValueError("learn must name some of %s, got %r" % (_BLOCKS, tuple(learn)))
     learn = tuple(b for b in _BLOCKS if b in tuple(learn))
     mats = learn != ("kd",)
     groups = {}  # geometry key -> device Scene
+    handles = {}  # ... -> its Views (views given)
     tasks = []
     for k, f in enumerate(files):
         host = Scene.from_file(f, device=False)
         key = _geometry_key(host, mats)
         if key not in groups:
             groups[key] = Scene.from_file(f)
+            if cams is not None:
+                handles[key] = groups[key].views(cams)
         truth = torch.tensor(host.materials, device=device)
         kd0 = torch.full_like(truth, init) if "kd" in learn else truth.clone()
-        task = SceneTask(f, groups[key], truth, None, kd0.requires_grad_("kd" in learn), index=first_index + k)
+        task = SceneTask(f, groups[key], truth, None, kd0.requires_grad_("kd" in learn), index=first_index + k,
+                         views=handles.get(key))
         if mats:
             _, ks, ke, _ = host.material_params()
             lobe = torch.tensor(host.lobe_mask, device=device)[:, None].float().expand(-1, 3)
@@ -158,7 +182,13 @@ def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_
             for idx in _runs(mine, tasks, target_chunk):
                 kd = torch.stack([tasks[i].truth for i in idx])
                 s0 = seed + 10**9 + tasks[idx[0]].index * stride
-                if mats:
+                if cams is not None:
+                    img = torch_ops.render_views_batch(
+                        sc, tasks[idx[0]].views, kd,
+                        torch.stack([tasks[i].truth_ks for i in idx]) if mats else None,
+                        torch.stack([tasks[i].truth_ke for i in idx]) if mats else None, width, height, target_spp,
+                        max_bounces, seed=seed + 10**9 + tasks[idx[0]].index * len(cams) * stride, seed_stride=stride)
+                elif mats:
                     img = torch_ops.render_materials_batch(sc, kd, torch.stack([tasks[i].truth_ks for i in idx]),
                                                            torch.stack([tasks[i].truth_ke for i in idx]), width,
                                                            height, target_spp, max_bounces, seed=s0,
@@ -198,13 +228,26 @@ class MaterialOptimizer:
     blocks do not act on are masked (scene.lobe_mask for Ks, scene.emitter_mask
     for Ke: structure is frozen at load); Kd and Ks are clamped to [0, 1], Ke to
     [0, inf).  `lr` may then be a dict per block, e.g. {"ks": 0.02, "ke":
-    0.2} (emission lives on another scale).  tie_shared is a Kd-only feature."""
+    0.2} (emission lives on another scale).  tie_shared is a Kd-only feature.
+
+    views, (V, 4, 4) camera matrices (the tasks come from
+    ``build_tasks(views=...)``: targets (V, H, W, 3)): every batch renders
+    through torch_ops.render_views_batch, for every `learn`, ("kd",) included
+    -- one forward and one adjoint launch over the batch's S x V (scene, view)
+    pairs; a scene's loss is the mean over (V, H, W, 3).  Step t of the job
+    then takes frames [2 t T V, 2 (t + 1) T V) with T = n_total: scene i view
+    b's forward is frame 2 t T V + i V + b, its adjoint T V frames later, so a
+    rank of a scene-parallel split still traces the one-rank run's samples.
+    tie_shared together with views raises ValueError."""
 
     def __init__(self, tasks: List[SceneTask], width: int, height: int, spp: int, max_bounces: int,
                  lr: Union[float, Dict[str, float]] = 1e-2, tie_shared: Optional[int] = None, seed: int = 0,
                  flush_every: int = 16, decorrelate: bool = True, n_total: Optional[int] = None,
-                 learn: Sequence[str] = ("kd",)):
+                 learn: Sequence[str] = ("kd",), views=None):
         self.tasks, self.W, self.H, self.spp, self.mb = tasks, width, height, spp, max_bounces
+        self.cams = None if views is None else _view_cams(views)
+        if self.cams is not None and tie_shared:
+            raise ValueError("MaterialOptimizer: tie_shared is not supported together with views")
         if not tuple(learn) or set(learn) - set(_BLOCKS):
             raise ValueError("learn must name some of %s, got %r" % (_BLOCKS, tuple(learn)))
         self.learn = tuple(b for b in _BLOCKS if b in tuple(learn))
@@ -229,7 +272,21 @@ class MaterialOptimizer:
         self.shared = None
         self.step_count = 0
         self.pending = []  # (tasks, per-scene loss tensor) in step order
-        if self.learn != ("kd",):
+        self.view_handles = []  # per batch (views given)
+        if self.cams is not None:
+            made = {}  # geometry handle -> Views: the tasks' own when they hold these cameras
+            for sc, ts in self.batches:
+                if id(sc) not in made:
+                    own = ts[0].views
+                    reuse = own is not None and np.array_equal(own.cams, self.cams)
+                    made[id(sc)] = own if reuse else sc.views(self.cams)
+                self.view_handles.append(made[id(sc)])
+                want = (len(self.cams), height, width, 3)
+                for t in ts:
+                    if tuple(t.target.shape) != want:
+                        raise ValueError("MaterialOptimizer: views need targets of shape %s (build_tasks(views=...)), "
+                                         "got %s" % (want, tuple(t.target.shape)))
+        if self.learn != ("kd",) or self.cams is not None:
             self._init_materials(lr, tie_shared)
             return
         if isinstance(lr, dict):
@@ -285,12 +342,22 @@ class MaterialOptimizer:
     def _step_materials(self):
         self.opt.zero_grad(set_to_none=False)
         step, T = self.step_count, self.n_total
-        for (sc, ts), leaf, fixed, mask, target, n_before in zip(self.batches, self.leaves, self.fixed, self.masks,
-                                                                 self.targets, self.offsets):
+        for k, ((sc, ts), leaf, fixed, mask, target, n_before) in enumerate(zip(
+                self.batches, self.leaves, self.fixed, self.masks, self.targets, self.offsets)):
             v = {b: leaf[b] if b in leaf else fixed[b] for b in _BLOCKS}
             for b in ("ks", "ke"):  # frozen rows: no value, no gradient
                 if b in leaf:
                     v[b] = leaf[b] * mask[b]
+            if self.cams is not None:  # S x V pairs, V frames per scene
+                V = len(self.cams)
+                base = self.seed + (2 * step * T + n_before) * V * self.frame
+                img = torch_ops.render_views_batch(
+                    sc, self.view_handles[k], v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, self.mb, seed=base,
+                    seed_stride=self.frame, adjoint_seed=(base + T * V * self.frame) if self.decorrelate else None)
+                per_scene = ((img - target) ** 2).mean(dim=(1, 2, 3, 4))
+                per_scene.sum().backward()
+                self.pending.append((ts, per_scene.detach()))
+                continue
             base = self.seed + (2 * step * T + n_before) * self.frame
             img = torch_ops.render_materials_batch(
                 sc, v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, self.mb, seed=base, seed_stride=self.frame,
@@ -309,7 +376,7 @@ class MaterialOptimizer:
 
     def step(self):
         """One Adam step over every scene (no host synchronisation)."""
-        if self.learn != ("kd",):
+        if self.learn != ("kd",) or self.cams is not None:
             return self._step_materials()
         self.opt.zero_grad(set_to_none=False)
         step = self.step_count

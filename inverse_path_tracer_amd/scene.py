@@ -415,6 +415,65 @@ class Scene:
                                               torch.cuda.current_stream(a.device).cuda_stream), "adjoint_views")
         return g.cpu().numpy()
 
+    def _view_sets_dev(self, views, kd, ks, ke, n_sets):
+        """Device copies of (S, nT, 3) host arrays (None stays None) and S:
+        the arrays' shared first extent, or n_sets when all are None."""
+        import torch
+
+        if views.scene is not self:
+            raise ValueError("the views belong to another scene")
+        host = [None if v is None else np.ascontiguousarray(np.asarray(v, np.float32)) for v in (kd, ks, ke)]
+        given = [v for v in host if v is not None]
+        S = int(n_sets) if n_sets is not None else (given[0].shape[0] if given and given[0].ndim == 3 else 1)
+        for name, v in zip(("kd", "ks", "ke"), host):
+            if v is not None and v.shape != (S, self.nT, 3):
+                raise ValueError("%s must be (S=%d, nT=%d, 3), got %s" % (name, S, self.nT, v.shape))
+        dev = [None if v is None else torch.from_numpy(v).cuda() for v in host]
+        return torch, S, dev, [None if t is None else t.data_ptr() for t in dev]
+
+    def render_views_batch(self, views, kd=None, ks=None, ke=None, width=0, height=0, spp=1, max_bounces=4, seed=0,
+                           seed_stride=None, row_begin=0, row_end=None, row_step=1, n_sets=None):
+        """HDR images (S, V, rows, W, 3) of S material sets through every view
+        from ONE launch (ipt_render_views_batch_dev): kd / ks / ke are
+        (S, nT, 3) host arrays or None (the scene's own values in every set;
+        all None: give n_sets).  Pair (s, b) traces seed + (s * V + b) *
+        seed_stride (default: one frame of samples) and equals view b of
+        ``render_views`` with set s's arrays at that seed bit for bit.
+        Bounded estimator only (max_bounces 0..62).  torch only provides the
+        device memory."""
+        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, n_sets)
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        hdr = torch.zeros((max(S, 0), len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
+        N.check(N.lib().ipt_render_views_batch_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0], ptr[1],
+                                                   ptr[2], hdr.data_ptr(),
+                                                   torch.cuda.current_stream(hdr.device).cuda_stream),
+                "render_views_batch")
+        return hdr.cpu().numpy()
+
+    def adjoint_views_batch(self, views, adj, kd=None, ks=None, ke=None, width=0, height=0, spp=1, max_bounces=4,
+                            seed=0, seed_stride=None, row_begin=0, row_end=None, row_step=1):
+        """Per material set s, d(sum over views of sum(adj[s, b] * I[s, b]))/
+        d(Kd, Ks, Ke): three (S, nT, 3) float64 blocks from ONE launch
+        (ipt_adjoint_views_batch_dev); adj is (S, V, H, W, 3) full frames,
+        kd / ks / ke as in ``render_views_batch``.  ``out[k][s]`` equals block
+        k of ``adjoint_views`` with set s's arrays at seed + s * V *
+        seed_stride, to the order of the fp64 atomics."""
+        adj = np.ascontiguousarray(np.asarray(adj, np.float32))
+        if adj.ndim != 5 or adj.shape[1:] != (len(views), height, width, 3):
+            raise ValueError("adj must be (S, V=%d, H=%d, W=%d, 3), got %s" % (len(views), height, width, adj.shape))
+        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, adj.shape[0])
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        a = torch.from_numpy(adj).cuda()
+        g = torch.zeros((max(S, 0), 3, self.nT, 3), device=a.device, dtype=torch.float64)
+        N.check(N.lib().ipt_adjoint_views_batch_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0], ptr[1],
+                                                    ptr[2], a.data_ptr(), g.data_ptr(),
+                                                    torch.cuda.current_stream(a.device).cuda_stream),
+                "adjoint_views_batch")
+        g = g.cpu().numpy()
+        return g[:, 0].copy(), g[:, 1].copy(), g[:, 2].copy()
+
     def view_rays(self, views, view, width, height, spp, seed, sample_index):
         """(origins, directions), (n, 3) float32 each: the camera rays of view
         `view` for the global sample indices (pixel * spp + sample), from the
