@@ -336,6 +336,25 @@ int ipt_adjoint_views_batch_dev(void *scene, void *views, const ipt_params_t *p,
                                 const float *kd_dev, const float *ks_dev, const float *ke_dev,
                                 const float *adj_dev /* [n_sets][V][H][W][3], full frames */,
                                 double *grad_dev /* [n_sets][Kd|Ks|Ke][nT][3], accumulated */, void *stream);
+/* The same pair for the reference's own estimator (no bounce cap; DESIGN.md
+ * §21): p->max_bounces must be -1.  Layouts, seeds, NULL arrays, the row band
+ * and row_step as above; pair (s, b) of the render equals view b of
+ * ipt_render_views_dev at -1 bit for bit, and with the scene's own camera as
+ * the one view the adjoint equals ipt_adjoint_mat_unbounded_dev's per set.
+ * Refused with a message before anything is enqueued: max_bounces >= 0 (the
+ * bounded pair above takes 0..62), n_sets < 1, n_sets*V > 65535, more than
+ * 65535 triangles, a views handle of another scene (or one not live), bins
+ * and tables that leave no room for one record slot per lane in 160 KiB. */
+int ipt_render_views_batch_unbounded_dev(void *scene, void *views, const ipt_params_t *p, int n_sets,
+                                         uint64_t seed_stride, const float *kd_dev, const float *ks_dev,
+                                         const float *ke_dev, /* n_sets*nT*3 or NULL */
+                                         float *hdr_dev /* [n_sets][V][rows][W][3] */, void *stream);
+int ipt_adjoint_views_batch_unbounded_dev(void *scene, void *views, const ipt_params_t *p, int n_sets,
+                                          uint64_t seed_stride, const float *kd_dev, const float *ks_dev,
+                                          const float *ke_dev,
+                                          const float *adj_dev /* [n_sets][V][H][W][3], full frames */,
+                                          double *grad_dev /* [n_sets][Kd|Ks|Ke][nT][3], accumulated */,
+                                          void *stream);
 /* Host-memory forms with the scene's own materials (synchronous). */
 int ipt_render_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride,
                           float *hdr /*V*rows*W*3*/);

@@ -122,7 +122,9 @@ SIGNATURES = {
     "ipt_adjoint_views_dev": (C.c_int, [vp, vp, pp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
     "ipt_render_views_batch_dev": (C.c_int, [vp, vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp]),
     "ipt_adjoint_views_batch_dev": (C.c_int, [vp, vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp]),
-    "ipt_render_views_host": (C.c_int, [vp, vp, pp, C.c_uint64, fp]),
+    "ipt_render_views_batch_unbounded_dev": (C.c_int, [vp, vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp]),
+    "ipt_adjoint_views_batch_unbounded_dev": (C.c_int, [vp, vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+    "ipt_render_views_host":(C.c_int, [vp, vp, pp, C.c_uint64, fp]),
     "ipt_adjoint_views_host": (C.c_int, [vp, vp, pp, C.c_uint64, fp, dp]),
     "ipt_views_rays_host": (C.c_int, [vp, vp, C.c_int, pp, C.c_int64, C.POINTER(C.c_int64), fp, fp]),
     "ipt_scene_set_accel": (C.c_int, [vp, C.c_int]),

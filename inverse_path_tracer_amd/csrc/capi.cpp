@@ -679,6 +679,36 @@ int ipt_adjoint_views_batch_dev(void *scene, void *views, const ipt_params_t *p,
                                                  adj_dev, grad_dev, stream));
 }
 
+// ---- views x material sets at no bounce cap
+int ipt_render_views_batch_unbounded_dev(void *scene, void *views, const ipt_params_t *p, int n_sets,
+                                         uint64_t seed_stride, const float *kd_dev, const float *ks_dev,
+                                         const float *ke_dev, float *hdr_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_render_views_batch_unbounded_dev") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || !hdr_dev) {
+    fail("ipt_render_views_batch_unbounded_dev: bad arguments (params and hdr_dev are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_render_views_batch_unbounded(s, v, views_params(p, seed_stride), n_sets, kd_dev, ks_dev,
+                                                          ke_dev, hdr_dev, stream));
+}
+
+int ipt_adjoint_views_batch_unbounded_dev(void *scene, void *views, const ipt_params_t *p, int n_sets,
+                                          uint64_t seed_stride, const float *kd_dev, const float *ks_dev,
+                                          const float *ke_dev, const float *adj_dev, double *grad_dev,
+                                          void *stream) {
+  GpuScene *s = as_scene(scene);
+  ipt::GpuViews *v = s ? as_views(views, "ipt_adjoint_views_batch_unbounded_dev") : nullptr;
+  if (!s || !v) return -1;
+  if (!p || !adj_dev || !grad_dev) {
+    fail("ipt_adjoint_views_batch_unbounded_dev: bad arguments (params, adj_dev and grad_dev are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_adjoint_views_batch_unbounded(s, v, views_params(p, seed_stride), n_sets, kd_dev, ks_dev,
+                                                           ke_dev, adj_dev, grad_dev, stream));
+}
+
 int ipt_render_views_host(void *scene, void *views, const ipt_params_t *p, uint64_t seed_stride, float *hdr) {
   GpuScene *s = as_scene(scene);
   ipt::GpuViews *v = s ? as_views(views, "ipt_render_views_host") : nullptr;

@@ -88,6 +88,13 @@ int gpu_render_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n
 int gpu_adjoint_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
                             const float *ks_dev, const float *ke_dev, const float *adj_dev, double *grad_dev,
                             void *stream);
+// The same pair at max_bounces = -1: the forward runs the view sets' forward kernels, the
+// adjoint one launch of trace_matu_views_batch_kernel.  Both refuse max_bounces >= 0.
+int gpu_render_views_batch_unbounded(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                                     const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream);
+int gpu_adjoint_views_batch_unbounded(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                                      const float *ks_dev, const float *ke_dev, const float *adj_dev,
+                                      double *grad_dev, void *stream);
 int gpu_render_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, float *hdr);
 int gpu_adjoint_views_host(GpuScene *s, const GpuViews *v, const RenderParams &p, const float *adj, double *grad);
 // The camera rays of view `view` for n global sample indices (host arrays; diagnostic).

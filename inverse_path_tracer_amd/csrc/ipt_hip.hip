@@ -965,6 +965,33 @@ trace_mat_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ ise
 #include "trace_body.h"
 }
 
+// The unbounded material adjoint over (material set, view) pairs (DESIGN.md
+// §21): trace_matu_kernel's ring, replays and carried words with the view
+// sets' keying -- seed, adjoint image and grab counter by the launch set, kd,
+// mat, kd/pi and the gradient slice by the material set, the camera (the
+// replays' too: they restart through the loop's own copy of the arguments) by
+// the view.  Bounds as trace_matu_kernel's, trailing parameters as
+// trace_mat_views_batch_kernel's.  A __global__ of its own, named so that no
+// count of the other families by prefix sees it.
+template <bool SPEC, bool BVH>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
+                          amdgpu_waves_per_eu(min_blocks<MODE_ADJU, BVH>()))) void
+trace_matu_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+                              const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat,
+                              const float *__restrict__ kd, const int *__restrict__ emit_tri,
+                              const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+                              float *__restrict__ out_samples, const float *__restrict__ adj,
+                              double *__restrict__ grad, const uint8_t *__restrict__ target,
+                              double *__restrict__ edges, const int *__restrict__ tri_emit,
+                              const float *__restrict__ views, const int nviews) {
+  constexpr int MODE = MODE_ADJU;
+  constexpr bool MATG = true;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = true;
+  constexpr bool VSETS = true;
+#include "trace_body.h"
+}
+
 // The diagnostic of ipt_views_rays_host: the megakernel's own rng_init and
 // camera_ray for caller-chosen global sample indices g (pixel = g / spp, row
 // major) of view `view`, written out as rays.
@@ -1119,7 +1146,8 @@ static std::vector<double> pmf_reciprocals(const std::vector<float> &pmf) {
 // KIND_VFWD / KIND_VMAT: the views' forward and bounded material adjoint
 // (trace_fwd_views_kernel, trace_mat_views_kernel).
 // KIND_VBFWD / KIND_VBMAT: the same over (material set, view) pairs
-// (trace_fwd_views_batch_kernel, trace_mat_views_batch_kernel).
+// (trace_fwd_views_batch_kernel, trace_mat_views_batch_kernel);
+// KIND_VBMAT at MODE_ADJU: the unbounded trace_matu_views_batch_kernel (§21).
 enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4, KIND_VBFWD = 5, KIND_VBMAT = 6 };
 constexpr int kKindLast = KIND_VBMAT;
 constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }  // ONE material set
@@ -1128,7 +1156,8 @@ constexpr bool kind_view_sets(int kind) { return kind == KIND_VBFWD || kind == K
 constexpr bool inst_valid(int mode, int kind) {
   return kind == KIND_TRACE  ? mode >= MODE_FWD && mode <= MODE_ADJW
          : kind == KIND_MATG ? mode == MODE_ADJ || mode == MODE_ADJU
-         : kind == KIND_VMAT || kind == KIND_VBMAT ? mode == MODE_ADJ
+         : kind == KIND_VMAT ? mode == MODE_ADJ
+         : kind == KIND_VBMAT ? mode == MODE_ADJ || mode == MODE_ADJU
                              : mode == MODE_FWD || mode == MODE_FWDM;
 }
 // An instance's slot in GpuScene::inst.  0..23: trace_kernel<mode, spec, bvh>;
@@ -1136,27 +1165,28 @@ constexpr bool inst_valid(int mode, int kind) {
 // spec, bvh>; 36..39: trace_matu_kernel<spec, bvh>; 40..47:
 // trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh>;
 // 52..59: trace_fwd_views_batch_kernel<FWD | FWDM, spec, bvh>; 60..63:
-// trace_mat_views_batch_kernel<spec, bvh>.
+// trace_mat_views_batch_kernel<spec, bvh>; 64..67:
+// trace_matu_views_batch_kernel<spec, bvh>.
 constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
   return (kind == KIND_MATG   ? (mode == MODE_ADJU ? 36 : 24)
           : kind == KIND_FWDB ? 28 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VFWD ? 40 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VMAT ? 48
           : kind == KIND_VBFWD ? 52 + (mode == MODE_FWDM ? 4 : 0)
-          : kind == KIND_VBMAT ? 60
+          : kind == KIND_VBMAT ? (mode == MODE_ADJU ? 64 : 60)
                               : mode * 4) +
          (spec ? 2 : 0) + (bvh ? 1 : 0);
 }
 // One past the largest slot of a valid instance, or -1 when two share a slot.
 constexpr int inst_slot_count() {
-  uint64_t seen = 0;
+  bool seen[128] = {};
   int n = 0;
   for (int kind = KIND_TRACE; kind <= kKindLast; ++kind)
     for (int mode = MODE_FWD; mode <= MODE_ADJW; ++mode)
       for (int sb = 0; sb < 4 && inst_valid(mode, kind); ++sb) {
         const int slot = inst_slot(mode, (sb & 2) != 0, (sb & 1) != 0, kind);
-        if (slot < 0 || slot >= 64 || (seen >> slot & 1)) return -1;
-        seen |= 1ull << slot;
+        if (slot < 0 || slot >= 128 || seen[slot]) return -1;
+        seen[slot] = true;
         n = slot + 1 > n ? slot + 1 : n;
       }
   return n;
@@ -1200,6 +1230,8 @@ struct GpuScene {
   int adju_nl = 0;       // ... made for this LDS base
   size_t matu_base = 0;  // gpu_adjoint_mat_unbounded's own choice (trace_matu_kernel's occupancy) ...
   int matu_nl = 0;       // ... for its LDS base
+  size_t vbmatu_base = 0;  // gpu_adjoint_views_batch_unbounded's (trace_matu_views_batch_kernel's occupancy) ...
+  int vbmatu_nl = 0;       // ... for its LDS base
   int *grad_map = nullptr, *slot_tri = nullptr;  // ADJ hot-set LDS slots (large scenes)
   int *tri_emit = nullptr;  // triangle -> emitter index or -1 (material overrides and adjoint)
   InstCache inst[kInstSlots];  // by inst_slot()
@@ -1420,8 +1452,9 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr auto kernel_of() {
   if constexpr (KIND == KIND_VBMAT) {
-    static_assert(MODE == MODE_ADJ, "the view sets' adjoint is the bounded material adjoint");
-    return &trace_mat_views_batch_kernel<SPEC, BVH>;
+    static_assert(MODE == MODE_ADJ || MODE == MODE_ADJU, "the view sets' adjoint is the material adjoint, MODE_ADJ or MODE_ADJU");
+    if constexpr (MODE == MODE_ADJU) return &trace_matu_views_batch_kernel<SPEC, BVH>;
+    else return &trace_mat_views_batch_kernel<SPEC, BVH>;
   } else if constexpr (KIND == KIND_VBFWD) {
     static_assert(is_fwd<MODE>(), "the view sets' forward: forward instances only");
     return &trace_fwd_views_batch_kernel<MODE, SPEC, BVH>;
@@ -1445,7 +1478,7 @@ constexpr auto kernel_of() {
 // ... and its name, for the IPT_DEBUG_GRID prints.
 constexpr const char *kernel_name(int mode, int kind) {
   return kind == KIND_VBFWD  ? "trace_fwd_views_batch_kernel"
-         : kind == KIND_VBMAT ? "trace_mat_views_batch_kernel"
+         : kind == KIND_VBMAT ? (mode == MODE_ADJU ? "trace_matu_views_batch_kernel" : "trace_mat_views_batch_kernel")
          : kind == KIND_VFWD ? "trace_fwd_views_kernel"
          : kind == KIND_VMAT ? "trace_mat_views_kernel"
          : kind == KIND_MATG ? (mode == MODE_ADJU ? "trace_matu_kernel" : "trace_mat_kernel")
@@ -2509,6 +2542,90 @@ int gpu_adjoint_mat_unbounded(GpuScene *s, const RenderParams &p, const float *k
   LaunchIO io;
   io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.stream = (hipStream_t)stream;
   return launch<MODE_ADJU, KIND_MATG>(s, a, lds, io);
+}
+
+// ------------------------------------------------------------ views x material sets, unbounded
+// The unbounded material adjoint's LDS in front of its ring slots, in the view
+// sets' launch too (a workgroup holds one pair's bins, tables and carried
+// words): bins + tables + carry bytes + owner markers; *per = one slot per lane.
+static size_t matu_lds_base(const GpuScene *s, const TraceArgs &a, size_t *per) {
+  *per = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse) * kBlock * sizeof(float);
+  return mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
+         mat_carry_bytes(use_bvh(s)) + (size_t)kBlock * sizeof(uint32_t);
+}
+// What both entry points refuse before anything is enqueued -- the argument
+// checks first, so a host-only scene reports them too and itself last; the
+// forward refuses what its adjoint refuses (one contract for the pair).
+static int view_sets_unbounded_params(GpuScene *s, const GpuViews *v, RenderParams &p, int n_sets) {
+  if (p.max_bounces >= 0) {
+    gpu_set_error("unbounded views batch: max_bounces must be -1 (no bounce cap); ipt_render_views_batch_dev and ipt_adjoint_views_batch_dev take max_bounces in 0..62");
+    return -1;
+  }
+  if (n_sets < 1) {
+    gpu_set_error("unbounded views batch: n_sets must be >= 1");
+    return -1;
+  }
+  if ((int64_t)n_sets * v->n > 65535) {
+    gpu_set_error("unbounded views batch: at most 65535 (material set, view) pairs per launch (n_sets * n_views)");
+    return -1;
+  }
+  if (s->host.nT > kMaxAdjTris) {
+    gpu_set_error("unbounded views batch supports at most 65535 triangles");
+    return -1;
+  }
+  if (v->scene != s) {
+    gpu_set_error("views: the handle was created for another scene");
+    return -1;
+  }
+  p.nscenes = n_sets * v->n;
+  if (check_params(s, p)) return -1;
+  size_t per = 0;
+  const size_t base = matu_lds_base(s, adjoint_args(s, p), &per);
+  if (base + per > 160 * 1024) {  // no room for one slot per lane
+    gpu_set_error("unbounded views batch: the Kd/Ks/Ke bins and the scene's LDS tables plus one record slot per lane exceed 160 KiB");
+    return -1;
+  }
+  return 0;
+}
+
+// gpu_render_views_batch at max_bounces = -1: the view sets' forward kernels
+// render unbounded as they are (gpu_render_views accepts -1 too); pair (m, b)
+// is gpu_render_views' view b of set m's arrays at seed + (m * V + b) *
+// seed_stride and -1, bit for bit.
+int gpu_render_views_batch_unbounded(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                                     const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream) {
+  if (view_sets_unbounded_params(s, v, p, n_sets)) return -1;
+  StreamScratch tab, kdrep;  // freed behind the launch, in stream order
+  const TriMat *mat = nullptr;
+  if (batch_kd(s, &kd_dev, n_sets, (hipStream_t)stream, kdrep)) return -1;
+  if (pack_materials(s, ks_dev, ke_dev, n_sets, (hipStream_t)stream, tab, &mat)) return -1;
+  return render_impl<KIND_VBFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, mat, v->dev, v->n);
+}
+
+// gpu_adjoint_mat_unbounded over n_sets material sets x V views in one launch
+// of trace_matu_views_batch_kernel: grad_dev n_sets x 3 x nT x 3 doubles
+// [set][Kd | Ks | Ke][tri][c], accumulated; adj_dev [n_sets][V] full frames.
+int gpu_adjoint_views_batch_unbounded(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
+                                      const float *ks_dev, const float *ke_dev, const float *adj_dev,
+                                      double *grad_dev, void *stream) {
+  if (view_sets_unbounded_params(s, v, p, n_sets)) return -1;
+  TraceArgs a = adjoint_args(s, p);
+  size_t per = 0;
+  const size_t base = matu_lds_base(s, a, &per);
+  // ring slots in LDS for THIS kernel's occupancy, in a cache of its own
+  a.rec_cap = kAdjuRing;
+  if (ring_lds_slots<KIND_VBMAT>(s, base, per, use_bvh(s), &s->vbmatu_base, &s->vbmatu_nl, &a.rec_lds)) return -1;
+  // a forced or default count the base leaves no room for shrinks to what fits (>= 1)
+  a.rec_lds = (int)std::min<size_t>((size_t)a.rec_lds, (160 * 1024 - base) / per);
+  const size_t lds = base + (size_t)a.rec_lds * per;
+  StreamScratch tab, kdrep;
+  const TriMat *mat = nullptr;
+  if (batch_kd(s, &kd_dev, n_sets, (hipStream_t)stream, kdrep)) return -1;
+  if (pack_materials(s, ks_dev, ke_dev, n_sets, (hipStream_t)stream, tab, &mat)) return -1;
+  LaunchIO io;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.views = v->dev, io.nviews = v->n;
+  io.stream = (hipStream_t)stream;
+  return launch<MODE_ADJU, KIND_VBMAT>(s, a, lds, io);
 }
 
 // Bounded adjoint launches of at least this many samples (all material sets)

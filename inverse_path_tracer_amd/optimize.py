@@ -38,6 +38,11 @@ the ground-truth Kd with many more samples).
   (DESIGN.md §20): targets are (V, H, W, 3), a step is still one forward and
   one adjoint launch per batch (torch_ops.render_views_batch, S sets x V
   views), for every ``learn``.  Without ``views`` nothing changes.
+* No bounce cap: with ``max_bounces=None`` (or negative; the reference's own
+  estimator) the two materials paths above render targets and steps through
+  torch_ops.render_views_batch_unbounded -- without ``views``
+  through one view of the scene's own camera, at the ``views=None`` seeds.
+  The Kd-only path takes ``max_bounces=None`` as it always did.
 
     python -m inverse_path_tracer_amd.optimize --scenes assets/scenes --n 13 --steps 200
 """
@@ -121,6 +126,11 @@ def _geometry_key(sc: Scene, materials: bool = False) -> bytes:
     return np.concatenate(parts, axis=1).tobytes()
 
 
+def _unbounded(max_bounces) -> bool:
+    """The reference's own estimator: no bounce cap (None or negative)."""
+    return max_bounces is None or max_bounces < 0
+
+
 def _view_cams(views) -> np.ndarray:
     cams = np.ascontiguousarray(np.asarray(views, np.float32))
     if cams.ndim != 3 or cams.shape[0] < 1 or cams.shape[1:] != (4, 4):
@@ -176,13 +186,26 @@ def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_
         host.close()
         tasks.append(task)
     stride = width * height * target_spp
+    unbounded = _unbounded(max_bounces)
     with torch.no_grad():
         for sc in groups.values():
             mine = [i for i, t in enumerate(tasks) if t.scene is sc]
+            own = sc.views(sc.camera()) if unbounded and mats and cams is None else None
             for idx in _runs(mine, tasks, target_chunk):
                 kd = torch.stack([tasks[i].truth for i in idx])
                 s0 = seed + 10**9 + tasks[idx[0]].index * stride
-                if cams is not None:
+                if unbounded and (mats or cams is not None):
+                    # no bounce cap: S sets x V views in one launch; without views the
+                    # scene's own camera is the one view -- V = 1, the frames below are s0's
+                    vh = tasks[idx[0]].views if cams is not None else own
+                    img = torch_ops.render_views_batch_unbounded(
+                        sc, vh, kd,
+                        torch.stack([tasks[i].truth_ks for i in idx]) if mats else None,
+                        torch.stack([tasks[i].truth_ke for i in idx]) if mats else None, width, height, target_spp,
+                        seed=seed + 10**9 + tasks[idx[0]].index * len(vh) * stride, seed_stride=stride)
+                    if cams is None:
+                        img = img[:, 0]
+                elif cams is not None:
                     img = torch_ops.render_views_batch(
                         sc, tasks[idx[0]].views, kd,
                         torch.stack([tasks[i].truth_ks for i in idx]) if mats else None,
@@ -198,6 +221,8 @@ def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_
                                                  seed_stride=stride)
                 for j, i in enumerate(idx):
                     tasks[i].target = img[j].clone()
+            if own is not None:
+                own.close()
     return tasks
 
 
@@ -286,6 +311,16 @@ class MaterialOptimizer:
                     if tuple(t.target.shape) != want:
                         raise ValueError("MaterialOptimizer: views need targets of shape %s (build_tasks(views=...)), "
                                          "got %s" % (want, tuple(t.target.shape)))
+        # no bounce cap on the materials path: every batch renders through
+        # torch_ops.render_views_batch_unbounded; without views the scene's own
+        # camera is the one view (V = 1: the frames are the views=None ones)
+        self.unbounded = _unbounded(max_bounces)
+        if self.unbounded and self.cams is None and self.learn != ("kd",):
+            made = {}
+            for sc, ts in self.batches:
+                if id(sc) not in made:
+                    made[id(sc)] = sc.views(sc.camera())
+                self.view_handles.append(made[id(sc)])
         if self.learn != ("kd",) or self.cams is not None:
             self._init_materials(lr, tie_shared)
             return
@@ -348,6 +383,19 @@ class MaterialOptimizer:
             for b in ("ks", "ke"):  # frozen rows: no value, no gradient
                 if b in leaf:
                     v[b] = leaf[b] * mask[b]
+            if self.unbounded:  # S x V pairs, V frames per scene; views=None: the own camera, V = 1
+                vh = self.view_handles[k]
+                V = len(vh)
+                base = self.seed + (2 * step * T + n_before) * V * self.frame
+                img = torch_ops.render_views_batch_unbounded(
+                    sc, vh, v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, seed=base, seed_stride=self.frame,
+                    adjoint_seed=(base + T * V * self.frame) if self.decorrelate else None)
+                if self.cams is None:
+                    img = img[:, 0]
+                per_scene = ((img - target) ** 2).mean(dim=tuple(range(1, img.dim())))
+                per_scene.sum().backward()
+                self.pending.append((ts, per_scene.detach()))
+                continue
             if self.cams is not None:  # S x V pairs, V frames per scene
                 V = len(self.cams)
                 base = self.seed + (2 * step * T + n_before) * V * self.frame

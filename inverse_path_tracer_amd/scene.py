@@ -474,6 +474,47 @@ class Scene:
         g = g.cpu().numpy()
         return g[:, 0].copy(), g[:, 1].copy(), g[:, 2].copy()
 
+    def render_views_batch_unbounded(self, views, kd=None, ks=None, ke=None, width=0, height=0, spp=1, seed=0,
+                                     seed_stride=None, row_begin=0, row_end=None, row_step=1, n_sets=None):
+        """``render_views_batch`` for the reference's own estimator (no bounce
+        cap): (S, V, rows, W, 3) from ONE launch
+        (ipt_render_views_batch_unbounded_dev).  Pair (s, b) equals view b of
+        ``render_views`` at ``max_bounces=None`` with set s's arrays at seed +
+        (s * V + b) * seed_stride bit for bit."""
+        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, n_sets)
+        p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        hdr = torch.zeros((max(S, 0), len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
+        N.check(N.lib().ipt_render_views_batch_unbounded_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0],
+                                                             ptr[1], ptr[2], hdr.data_ptr(),
+                                                             torch.cuda.current_stream(hdr.device).cuda_stream),
+                "render_views_batch_unbounded")
+        return hdr.cpu().numpy()
+
+    def adjoint_views_batch_unbounded(self, views, adj, kd=None, ks=None, ke=None, width=0, height=0, spp=1, seed=0,
+                                      seed_stride=None, row_begin=0, row_end=None, row_step=1):
+        """``adjoint_views_batch`` for the reference's own estimator (no bounce
+        cap): three (S, nT, 3) float64 blocks from ONE launch of the unbounded
+        material adjoint over (set, view) pairs
+        (ipt_adjoint_views_batch_unbounded_dev); adj is (S, V, H, W, 3) full
+        frames.  With the scene's own camera as the one view, ``out[k][s]``
+        equals block k of ``adjoint_materials_unbounded`` with set s's
+        materials at seed + s * seed_stride, to the order of the fp64 atomics."""
+        adj = np.ascontiguousarray(np.asarray(adj, np.float32))
+        if adj.ndim != 5 or adj.shape[1:] != (len(views), height, width, 3):
+            raise ValueError("adj must be (S, V=%d, H=%d, W=%d, 3), got %s" % (len(views), height, width, adj.shape))
+        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, adj.shape[0])
+        p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        a = torch.from_numpy(adj).cuda()
+        g = torch.zeros((max(S, 0), 3, self.nT, 3), device=a.device, dtype=torch.float64)
+        N.check(N.lib().ipt_adjoint_views_batch_unbounded_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0],
+                                                              ptr[1], ptr[2], a.data_ptr(), g.data_ptr(),
+                                                              torch.cuda.current_stream(a.device).cuda_stream),
+                "adjoint_views_batch_unbounded")
+        g = g.cpu().numpy()
+        return g[:, 0].copy(), g[:, 1].copy(), g[:, 2].copy()
+
     def view_rays(self, views, view, width, height, spp, seed, sample_index):
         """(origins, directions), (n, 3) float32 each: the camera rays of view
         `view` for the global sample indices (pixel * spp + sample), from the

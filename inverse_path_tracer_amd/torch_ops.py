@@ -413,3 +413,56 @@ def render_views_batch(scene: Scene, views, kd, ks, ke, width: int, height: int,
     stride = width * height * spp if seed_stride is None else int(seed_stride)
     p = N.make_params(width, height, spp, max_bounces, seed)
     return _RenderViewsBatchFn.apply(kd, ks, ke, scene, views, p, stride, adjoint_seed)
+
+
+class _RenderViewsBatchUnboundedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kd, ks, ke, scene, views, params, stride, adjoint_seed):
+        given = [t for t in (kd, ks, ke) if t is not None]
+        dev, S = given[0].device, given[0].shape[0]
+        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
+        hdr = torch.empty((S, len(views), params.height, params.width, 3), device=dev, dtype=torch.float32)
+        N.check(N.lib().ipt_render_views_batch_unbounded_dev(scene.handle, views.handle, C.byref(params), S, stride,
+                                                             _ptr(c[0]), _ptr(c[1]), _ptr(c[2]), hdr.data_ptr(),
+                                                             _stream(dev)), "ipt_render_views_batch_unbounded_dev")
+        ctx.scene, ctx.views, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat, ctx.S = (scene, views, params, stride,
+                                                                                         adjoint_seed, c, S)
+        return hdr
+
+    @staticmethod
+    def backward(ctx, grad_hdr):
+        p = _replay_params(ctx.params, ctx.adjoint_seed)
+        kd, ks, ke = ctx.mat
+        adj = grad_hdr.float().contiguous()
+        g = torch.zeros((ctx.S, 3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
+        N.check(N.lib().ipt_adjoint_views_batch_unbounded_dev(ctx.scene.handle, ctx.views.handle, C.byref(p), ctx.S,
+                                                              ctx.stride, _ptr(kd), _ptr(ks), _ptr(ke), adj.data_ptr(),
+                                                              g.data_ptr(), _stream(adj.device)),
+                "ipt_adjoint_views_batch_unbounded_dev")
+        out = [g[:, i].float() if (t is not None and ctx.needs_input_grad[i]) else None
+               for i, t in enumerate((kd, ks, ke))]
+        return out[0], out[1], out[2], None, None, None, None, None
+
+
+def render_views_batch_unbounded(scene: Scene, views, kd, ks, ke, width: int, height: int, spp: int, seed: int = 0,
+                                 seed_stride=None, adjoint_seed=None) -> torch.Tensor:
+    """``render_views_batch`` for the reference's own estimator (no bounce cap,
+    paths end by Russian roulette or a miss): kd, ks, ke (S, nT, 3) CUDA
+    tensors as there -> HDR images (S, V, H, W, 3).  ONE forward launch
+    (ipt_render_views_batch_unbounded_dev) and ONE backward launch of the
+    unbounded material adjoint over the S * V pairs
+    (ipt_adjoint_views_batch_unbounded_dev), float32 gradients
+    for the inputs that require them, None for the others.  Seeds, masks and
+    `adjoint_seed` as in ``render_views_batch``."""
+    given = [t for t in (kd, ks, ke) if t is not None]
+    if not given:
+        raise ValueError("render_views_batch_unbounded needs at least one of kd, ks, ke as a device tensor")
+    for t in given:
+        if t.dim() != 3 or tuple(t.shape[1:]) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (S, nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+        if t.shape[0] != given[0].shape[0]:
+            raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
+                             [tuple(u.shape) for u in given])
+    stride = width * height * spp if seed_stride is None else int(seed_stride)
+    p = N.make_params(width, height, spp, None, seed)
+    return _RenderViewsBatchUnboundedFn.apply(kd, ks, ke, scene, views, p, stride, adjoint_seed)
