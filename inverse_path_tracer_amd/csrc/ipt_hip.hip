@@ -2116,6 +2116,18 @@ static int batch_kd(GpuScene *s, const float **kd_dev, int sets, hipStream_t st,
   return 0;
 }
 
+// What a material launch reads besides the scene: its kd (batch_kd) and its
+// TriMat tables (pack_materials), enqueued on the launch's stream in that
+// order; the scratch is freed behind the launch, in stream order.
+struct LaunchMaterials {
+  StreamScratch tab, kdrep;
+  const TriMat *mat = nullptr;
+  int fill(GpuScene *s, const float **kd_dev, const float *ks_dev, const float *ke_dev, int sets, void *stream) {
+    if (batch_kd(s, kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
+    return pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat);
+  }
+};
+
 // The batched material launches' limit on the number of sets, checked before
 // anything is enqueued.
 static int check_sets(int n_scenes) {
@@ -2129,11 +2141,9 @@ static int check_sets(int n_scenes) {
 static int render_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,
                            const float *ke_dev, float *hdr_dev, uint8_t *ldr_dev, void *stream) {
   const int sets = p.nscenes > 1 ? p.nscenes : 1;
-  StreamScratch tab, kdrep;  // freed behind the launch, in stream order
-  const TriMat *mat = nullptr;
-  if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
-  if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
-  return render_impl(s, p, kd_dev, hdr_dev, ldr_dev, stream, mat);
+  LaunchMaterials m;
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, sets, stream)) return -1;
+  return render_impl(s, p, kd_dev, hdr_dev, ldr_dev, stream, m.mat);
 }
 
 int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
@@ -2278,12 +2288,10 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
     return -1;
   }
   const int sets = view_sets > 0 ? view_sets : (p.nscenes > 1 && !views_dev) ? p.nscenes : 1;
-  StreamScratch tab, kdrep;
-  const TriMat *mat = nullptr;
-  if (batch_kd(s, &kd_dev, sets, (hipStream_t)stream, kdrep)) return -1;
-  if (pack_materials(s, ks_dev, ke_dev, sets, (hipStream_t)stream, tab, &mat)) return -1;
+  LaunchMaterials m;
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, sets, stream)) return -1;
   LaunchIO io;
-  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.views = views_dev, io.stream = (hipStream_t)stream;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = m.mat, io.views = views_dev, io.stream = (hipStream_t)stream;
   if (view_sets > 0) {
     io.nviews = p.nscenes / view_sets;
     return launch<MODE_ADJ, KIND_VBMAT>(s, a, lds, io);
@@ -2378,10 +2386,9 @@ int gpu_render_views(GpuScene *s, const GpuViews *v, RenderParams p, const float
     gpu_set_error("views: give max_bounces in 0..62, or -1 for the unbounded estimator");
     return -1;
   }
-  StreamScratch tab;
-  const TriMat *mat = nullptr;
-  if (pack_materials(s, ks_dev, ke_dev, 1, (hipStream_t)stream, tab, &mat)) return -1;
-  return render_impl<KIND_VFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, mat, v->dev);
+  LaunchMaterials m;  // (one set: the caller's kd or the scene's own, as it is)
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, 1, stream)) return -1;
+  return render_impl<KIND_VFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, m.mat, v->dev);
 }
 
 // d(sum over views of sum adj_b * I_b)/d(Kd, Ks, Ke): ONE gradient of 3 x nT x 3
@@ -2440,11 +2447,9 @@ int gpu_render_views_batch(GpuScene *s, const GpuViews *v, RenderParams p, int n
     gpu_set_error("views batch: LDS footprint (Kd/Ks/Ke bins + tables + vertex records) exceeds 160 KiB; lower max_bounces");
     return -1;
   }
-  StreamScratch tab, kdrep;  // freed behind the launch, in stream order
-  const TriMat *mat = nullptr;
-  if (batch_kd(s, &kd_dev, n_sets, (hipStream_t)stream, kdrep)) return -1;
-  if (pack_materials(s, ks_dev, ke_dev, n_sets, (hipStream_t)stream, tab, &mat)) return -1;
-  return render_impl<KIND_VBFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, mat, v->dev, v->n);
+  LaunchMaterials m;
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, n_sets, stream)) return -1;
+  return render_impl<KIND_VBFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, m.mat, v->dev, v->n);
 }
 
 // grad_dev: n_sets x 3 x nT x 3 doubles [set][Kd | Ks | Ke][tri][c],
@@ -2494,6 +2499,32 @@ int gpu_views_rays_host(GpuScene *s, const GpuViews *v, int view, RenderParams p
   return 0;
 }
 
+// The unbounded material adjoint's LDS in front of its ring slots, in the view
+// sets' launch too (a workgroup holds one pair's bins, tables and carried
+// words): bins (Kd, Ks with a lobe, Ke per emitter) + tables + the owners'
+// carried words + owner markers; *per = one ring slot per lane.
+static size_t matu_lds_base(const GpuScene *s, const TraceArgs &a, size_t *per) {
+  *per = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse) * kBlock * sizeof(float);
+  return mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
+         mat_carry_bytes(use_bvh(s)) + (size_t)kBlock * sizeof(uint32_t);
+}
+
+// The ring of an unbounded material adjoint (KIND_MATG, KIND_VBMAT) and the
+// launch's LDS bytes: the slots in LDS are chosen as gpu_adjoint chooses them
+// but for THIS kernel's occupancy, in the caller's own cache pair; a forced or
+// default count the base leaves no room for shrinks to what fits (>= 1: the
+// callers have refused a base with no room for one slot per lane).
+template <int KIND>
+static int matu_ring(GpuScene *s, TraceArgs &a, size_t *cached_base, int *cached_nl, size_t *lds) {
+  size_t per = 0;
+  const size_t base = matu_lds_base(s, a, &per);
+  a.rec_cap = kAdjuRing;
+  if (ring_lds_slots<KIND>(s, base, per, use_bvh(s), cached_base, cached_nl, &a.rec_lds)) return -1;
+  a.rec_lds = (int)std::min<size_t>((size_t)a.rec_lds, (160 * 1024 - base) / per);
+  *lds = base + (size_t)a.rec_lds * per;
+  return 0;
+}
+
 // dL/dKd, dL/dKs, dL/dKe of the reference's own estimator (no bounce cap) in
 // one launch of trace_matu_kernel: gpu_adjoint's unbounded
 // launch with the material adjoint's bins, overrides and tri_emit map.
@@ -2517,42 +2548,21 @@ int gpu_adjoint_mat_unbounded(GpuScene *s, const RenderParams &p, const float *k
     return -1;
   }
   TraceArgs a = adjoint_args(s, p);
-  const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
-  const size_t per = fields * kBlock * sizeof(float);  // one ring slot per lane
-  const bool bvh = use_bvh(s);
-  // bins (Kd, Ks with a lobe, Ke per emitter) + tables + the owners' carried words + owner markers
-  const size_t base = mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
-                      mat_carry_bytes(bvh) + (size_t)kBlock * sizeof(uint32_t);
-  // a base with no room for one slot per lane is refused
-  if (base + per > 160 * 1024) {
+  size_t per = 0, lds = 0;
+  if (matu_lds_base(s, a, &per) + per > 160 * 1024) {  // no room for one slot per lane
     gpu_set_error("unbounded material adjoint: the Kd/Ks/Ke bins and the scene's LDS tables plus one record slot per lane exceed 160 KiB");
     return -1;
   }
-  // ring slots in LDS, chosen as gpu_adjoint chooses them but for THIS
-  // kernel's occupancy and in a cache of its own: the bins are larger than
-  // the Kd-only adjoint's, so the count may differ
-  a.rec_cap = kAdjuRing;
-  if (ring_lds_slots<KIND_MATG>(s, base, per, bvh, &s->matu_base, &s->matu_nl, &a.rec_lds)) return -1;
-  // a forced or default count the base leaves no room for shrinks to what fits (>= 1)
-  a.rec_lds = (int)std::min<size_t>((size_t)a.rec_lds, (160 * 1024 - base) / per);
-  const size_t lds = base + (size_t)a.rec_lds * per;
-  StreamScratch tab;
-  const TriMat *mat = nullptr;
-  if (pack_materials(s, ks_dev, ke_dev, 1, (hipStream_t)stream, tab, &mat)) return -1;
+  // (its bins are larger than the Kd-only adjoint's, so its slot count and cache are its own)
+  if (matu_ring<KIND_MATG>(s, a, &s->matu_base, &s->matu_nl, &lds)) return -1;
+  LaunchMaterials m;  // (one set)
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, 1, stream)) return -1;
   LaunchIO io;
-  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.stream = (hipStream_t)stream;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = m.mat, io.stream = (hipStream_t)stream;
   return launch<MODE_ADJU, KIND_MATG>(s, a, lds, io);
 }
 
 // ------------------------------------------------------------ views x material sets, unbounded
-// The unbounded material adjoint's LDS in front of its ring slots, in the view
-// sets' launch too (a workgroup holds one pair's bins, tables and carried
-// words): bins + tables + carry bytes + owner markers; *per = one slot per lane.
-static size_t matu_lds_base(const GpuScene *s, const TraceArgs &a, size_t *per) {
-  *per = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse) * kBlock * sizeof(float);
-  return mat_lds_doubles(a.grad_slots, s->host.nE, s->has_ks) * sizeof(double) + table_bytes(a) +
-         mat_carry_bytes(use_bvh(s)) + (size_t)kBlock * sizeof(uint32_t);
-}
 // What both entry points refuse before anything is enqueued -- the argument
 // checks first, so a host-only scene reports them too and itself last; the
 // forward refuses what its adjoint refuses (one contract for the pair).
@@ -2595,11 +2605,9 @@ static int view_sets_unbounded_params(GpuScene *s, const GpuViews *v, RenderPara
 int gpu_render_views_batch_unbounded(GpuScene *s, const GpuViews *v, RenderParams p, int n_sets, const float *kd_dev,
                                      const float *ks_dev, const float *ke_dev, float *hdr_dev, void *stream) {
   if (view_sets_unbounded_params(s, v, p, n_sets)) return -1;
-  StreamScratch tab, kdrep;  // freed behind the launch, in stream order
-  const TriMat *mat = nullptr;
-  if (batch_kd(s, &kd_dev, n_sets, (hipStream_t)stream, kdrep)) return -1;
-  if (pack_materials(s, ks_dev, ke_dev, n_sets, (hipStream_t)stream, tab, &mat)) return -1;
-  return render_impl<KIND_VBFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, mat, v->dev, v->n);
+  LaunchMaterials m;
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, n_sets, stream)) return -1;
+  return render_impl<KIND_VBFWD>(s, p, kd_dev, hdr_dev, nullptr, stream, m.mat, v->dev, v->n);
 }
 
 // gpu_adjoint_mat_unbounded over n_sets material sets x V views in one launch
@@ -2610,20 +2618,12 @@ int gpu_adjoint_views_batch_unbounded(GpuScene *s, const GpuViews *v, RenderPara
                                       double *grad_dev, void *stream) {
   if (view_sets_unbounded_params(s, v, p, n_sets)) return -1;
   TraceArgs a = adjoint_args(s, p);
-  size_t per = 0;
-  const size_t base = matu_lds_base(s, a, &per);
-  // ring slots in LDS for THIS kernel's occupancy, in a cache of its own
-  a.rec_cap = kAdjuRing;
-  if (ring_lds_slots<KIND_VBMAT>(s, base, per, use_bvh(s), &s->vbmatu_base, &s->vbmatu_nl, &a.rec_lds)) return -1;
-  // a forced or default count the base leaves no room for shrinks to what fits (>= 1)
-  a.rec_lds = (int)std::min<size_t>((size_t)a.rec_lds, (160 * 1024 - base) / per);
-  const size_t lds = base + (size_t)a.rec_lds * per;
-  StreamScratch tab, kdrep;
-  const TriMat *mat = nullptr;
-  if (batch_kd(s, &kd_dev, n_sets, (hipStream_t)stream, kdrep)) return -1;
-  if (pack_materials(s, ks_dev, ke_dev, n_sets, (hipStream_t)stream, tab, &mat)) return -1;
+  size_t lds = 0;
+  if (matu_ring<KIND_VBMAT>(s, a, &s->vbmatu_base, &s->vbmatu_nl, &lds)) return -1;
+  LaunchMaterials m;
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, n_sets, stream)) return -1;
   LaunchIO io;
-  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = mat, io.views = v->dev, io.nviews = v->n;
+  io.kd = kd_dev, io.adj = adj_dev, io.grad = grad_dev, io.mat = m.mat, io.views = v->dev, io.nviews = v->n;
   io.stream = (hipStream_t)stream;
   return launch<MODE_ADJU, KIND_VBMAT>(s, a, lds, io);
 }

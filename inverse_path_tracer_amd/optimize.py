@@ -138,6 +138,43 @@ def _view_cams(views) -> np.ndarray:
     return cams
 
 
+def _route(learn, cams, max_bounces):
+    """(render, own_view): how targets and steps are rendered, for build_tasks
+    and MaterialOptimizer alike.  render(scene, views, kd, ks, ke, W, H, spp,
+    seed=, seed_stride=[, adjoint_seed=]) -> (S, [V,] H, W, 3) is one batched
+    torch_ops op; own_view: the caller passes a Views of the scene's own
+    camera as the single view (V = 1), and render drops the view axis.
+      1. learn ("kd",), no views, any max_bounces: render_batch;
+      2. no bounce cap: render_views_batch_unbounded, through
+         the own camera without views;
+      3. views: render_views_batch;  4. otherwise: render_materials_batch."""
+    mb = max_bounces
+    if learn == ("kd",) and cams is None:
+        return lambda sc, vh, kd, ks, ke, *frame, **seeds: torch_ops.render_batch(sc, kd, *frame, mb, **seeds), False
+    if _unbounded(mb):
+        own_view = cams is None
+
+        def render(sc, vh, *args, **seeds):
+            img = torch_ops.render_views_batch_unbounded(sc, vh, *args, **seeds)
+            return img[:, 0] if own_view else img
+        return render, own_view
+    if cams is not None:
+        return lambda sc, vh, *args, **seeds: torch_ops.render_views_batch(sc, vh, *args, mb, **seeds), False
+    return lambda sc, vh, *args, **seeds: torch_ops.render_materials_batch(sc, *args, mb, **seeds), False
+
+
+def _target_seed(seed, index, V, frame):
+    """Scene `index` view b is target frame index * V + b of the stream at seed + 10^9 (V = 1 without views)."""
+    return seed + 10**9 + index * V * frame
+
+
+def _step_seeds(seed, step, T, n_before, V, frame, decorrelate):
+    """(seed, adjoint_seed) of a batch whose first scene is n_before: step t of T scenes takes the frames
+    [2 t T V, 2 (t + 1) T V), the T V forward frames first (V = 1 without views)."""
+    base = seed + (2 * step * T + n_before) * V * frame
+    return base, (base + T * V * frame) if decorrelate else None
+
+
 def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_bounces: int, init: float,
                 device: torch.device, seed: int = 7, target_chunk: int = 16, first_index: int = 0,
                 learn: Sequence[str] = ("kd",), init_ks: float = 0.5, init_ke: float = 5.0,
@@ -185,40 +222,18 @@ def build_tasks(files: List[str], width: int, height: int, target_spp: int, max_
             task.ke = (emit * init_ke).requires_grad_(True) if "ke" in learn else task.truth_ke.clone()
         host.close()
         tasks.append(task)
-    stride = width * height * target_spp
-    unbounded = _unbounded(max_bounces)
+    frame = width * height * target_spp
+    render, own_view = _route(learn, cams, max_bounces)
     with torch.no_grad():
         for sc in groups.values():
             mine = [i for i, t in enumerate(tasks) if t.scene is sc]
-            own = sc.views(sc.camera()) if unbounded and mats and cams is None else None
+            own = sc.views(sc.camera()) if own_view else None
             for idx in _runs(mine, tasks, target_chunk):
-                kd = torch.stack([tasks[i].truth for i in idx])
-                s0 = seed + 10**9 + tasks[idx[0]].index * stride
-                if unbounded and (mats or cams is not None):
-                    # no bounce cap: S sets x V views in one launch; without views the
-                    # scene's own camera is the one view -- V = 1, the frames below are s0's
-                    vh = tasks[idx[0]].views if cams is not None else own
-                    img = torch_ops.render_views_batch_unbounded(
-                        sc, vh, kd,
-                        torch.stack([tasks[i].truth_ks for i in idx]) if mats else None,
-                        torch.stack([tasks[i].truth_ke for i in idx]) if mats else None, width, height, target_spp,
-                        seed=seed + 10**9 + tasks[idx[0]].index * len(vh) * stride, seed_stride=stride)
-                    if cams is None:
-                        img = img[:, 0]
-                elif cams is not None:
-                    img = torch_ops.render_views_batch(
-                        sc, tasks[idx[0]].views, kd,
-                        torch.stack([tasks[i].truth_ks for i in idx]) if mats else None,
-                        torch.stack([tasks[i].truth_ke for i in idx]) if mats else None, width, height, target_spp,
-                        max_bounces, seed=seed + 10**9 + tasks[idx[0]].index * len(cams) * stride, seed_stride=stride)
-                elif mats:
-                    img = torch_ops.render_materials_batch(sc, kd, torch.stack([tasks[i].truth_ks for i in idx]),
-                                                           torch.stack([tasks[i].truth_ke for i in idx]), width,
-                                                           height, target_spp, max_bounces, seed=s0,
-                                                           seed_stride=stride)
-                else:
-                    img = torch_ops.render_batch(sc, kd, width, height, target_spp, max_bounces, seed=s0,
-                                                 seed_stride=stride)
+                vh = own if own_view else tasks[idx[0]].views
+                kd, ks, ke = (torch.stack([getattr(tasks[i], b) for i in idx]) if mats or b == "truth" else None
+                              for b in ("truth", "truth_ks", "truth_ke"))
+                img = render(sc, vh, kd, ks, ke, width, height, target_spp, seed_stride=frame,
+                             seed=_target_seed(seed, tasks[idx[0]].index, 1 if vh is None else len(vh), frame))
                 for j, i in enumerate(idx):
                     tasks[i].target = img[j].clone()
             if own is not None:
@@ -314,8 +329,8 @@ class MaterialOptimizer:
         # no bounce cap on the materials path: every batch renders through
         # torch_ops.render_views_batch_unbounded; without views the scene's own
         # camera is the one view (V = 1: the frames are the views=None ones)
-        self.unbounded = _unbounded(max_bounces)
-        if self.unbounded and self.cams is None and self.learn != ("kd",):
+        self.render, own_view = _route(self.learn, self.cams, max_bounces)
+        if own_view:
             made = {}
             for sc, ts in self.batches:
                 if id(sc) not in made:
@@ -374,72 +389,50 @@ class MaterialOptimizer:
         self.params = [q for g in groups for q in g["params"]]
         self.opt = torch.optim.Adam([g for g in groups if g["params"]] or [{"params": []}])
 
+    def _forward_backward(self, k, kd, ks, ke):
+        """Batch k's forward on the frames of this step, the loss per scene (the mean over its [V,] H, W, 3)
+        and its backward on the step's adjoint frames: each scene's loss only reaches its own parameters."""
+        sc, ts = self.batches[k]
+        vh = self.view_handles[k] if self.view_handles else None
+        # step t uses 2 T V frames of the sample-index space: the T V forward frames, then the T V adjoint frames
+        seed, adjoint_seed = _step_seeds(self.seed, self.step_count, self.n_total, self.offsets[k],
+                                         1 if vh is None else len(vh), self.frame, self.decorrelate)
+        img = self.render(sc, vh, kd, ks, ke, self.W, self.H, self.spp, seed=seed, seed_stride=self.frame,
+                          adjoint_seed=adjoint_seed)
+        per_scene = ((img - self.targets[k]) ** 2).mean(dim=tuple(range(1, img.dim())))
+        per_scene.sum().backward()
+        self.pending.append((ts, per_scene.detach()))
+
+    def _end_step(self):
+        self.step_count += 1
+        if self.flush_every and self.step_count % self.flush_every == 0:
+            _flush_losses(self.pending)
+
     def _step_materials(self):
         self.opt.zero_grad(set_to_none=False)
-        step, T = self.step_count, self.n_total
-        for k, ((sc, ts), leaf, fixed, mask, target, n_before) in enumerate(zip(
-                self.batches, self.leaves, self.fixed, self.masks, self.targets, self.offsets)):
+        for k, (leaf, fixed, mask) in enumerate(zip(self.leaves, self.fixed, self.masks)):
             v = {b: leaf[b] if b in leaf else fixed[b] for b in _BLOCKS}
             for b in ("ks", "ke"):  # frozen rows: no value, no gradient
                 if b in leaf:
                     v[b] = leaf[b] * mask[b]
-            if self.unbounded:  # S x V pairs, V frames per scene; views=None: the own camera, V = 1
-                vh = self.view_handles[k]
-                V = len(vh)
-                base = self.seed + (2 * step * T + n_before) * V * self.frame
-                img = torch_ops.render_views_batch_unbounded(
-                    sc, vh, v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, seed=base, seed_stride=self.frame,
-                    adjoint_seed=(base + T * V * self.frame) if self.decorrelate else None)
-                if self.cams is None:
-                    img = img[:, 0]
-                per_scene = ((img - target) ** 2).mean(dim=tuple(range(1, img.dim())))
-                per_scene.sum().backward()
-                self.pending.append((ts, per_scene.detach()))
-                continue
-            if self.cams is not None:  # S x V pairs, V frames per scene
-                V = len(self.cams)
-                base = self.seed + (2 * step * T + n_before) * V * self.frame
-                img = torch_ops.render_views_batch(
-                    sc, self.view_handles[k], v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, self.mb, seed=base,
-                    seed_stride=self.frame, adjoint_seed=(base + T * V * self.frame) if self.decorrelate else None)
-                per_scene = ((img - target) ** 2).mean(dim=(1, 2, 3, 4))
-                per_scene.sum().backward()
-                self.pending.append((ts, per_scene.detach()))
-                continue
-            base = self.seed + (2 * step * T + n_before) * self.frame
-            img = torch_ops.render_materials_batch(
-                sc, v["kd"], v["ks"], v["ke"], self.W, self.H, self.spp, self.mb, seed=base, seed_stride=self.frame,
-                adjoint_seed=(base + T * self.frame) if self.decorrelate else None)
-            per_scene = ((img - target) ** 2).mean(dim=(1, 2, 3))
-            per_scene.sum().backward()
-            self.pending.append((ts, per_scene.detach()))
+            self._forward_backward(k, v["kd"], v["ks"], v["ke"])
         self.opt.step()
         with torch.no_grad():
             for leaf in self.leaves:
                 for b, q in leaf.items():
                     q.clamp_(0.0, None if b == "ke" else 1.0)  # emission has no upper bound
-        self.step_count += 1
-        if self.flush_every and self.step_count % self.flush_every == 0:
-            _flush_losses(self.pending)
+        self._end_step()
 
     def step(self):
         """One Adam step over every scene (no host synchronisation)."""
         if self.learn != ("kd",) or self.cams is not None:
             return self._step_materials()
         self.opt.zero_grad(set_to_none=False)
-        step = self.step_count
-        for (sc, ts), leaf, target, n_before in zip(self.batches, self.leaves, self.targets, self.offsets):
+        for k, ((_, ts), leaf) in enumerate(zip(self.batches, self.leaves)):
             kd = leaf
             if self.shared is not None:
                 kd = torch.cat([self.shared.unsqueeze(0).expand(len(ts), -1, -1), leaf[:, self.tie:]], dim=1)
-            # step t uses 2T frames of the sample-index space: the T forward frames, then the T adjoint frames
-            T = self.n_total
-            base = self.seed + (2 * step * T + n_before) * self.frame
-            img = torch_ops.render_batch(sc, kd, self.W, self.H, self.spp, self.mb, seed=base, seed_stride=self.frame,
-                                         adjoint_seed=(base + T * self.frame) if self.decorrelate else None)
-            per_scene = ((img - target) ** 2).mean(dim=(1, 2, 3))
-            per_scene.sum().backward()  # each scene's loss only reaches its own parameters
-            self.pending.append((ts, per_scene.detach()))
+            self._forward_backward(k, kd, None, None)
         if self.shared is not None:
             if self.shared.grad is None:
                 self.shared.grad = torch.zeros_like(self.shared)
@@ -448,9 +441,7 @@ class MaterialOptimizer:
         with torch.no_grad():
             for p in self.params:
                 p.clamp_(0.0, 1.0)
-        self.step_count += 1
-        if self.flush_every and self.step_count % self.flush_every == 0:
-            _flush_losses(self.pending)
+        self._end_step()
 
     def run(self, steps: int, log_every: int = 0):
         _, R = world()

@@ -321,31 +321,12 @@ class Scene:
         set); set b traces seed + b * seed_stride (default: one frame of
         samples).  Returns (S, 3, nT, 3) float64, [set][Kd | Ks | Ke].  torch
         only provides the device memory."""
-        import torch
-
         adj = np.ascontiguousarray(np.asarray(adj, np.float32))
         if adj.ndim != 4 or adj.shape[1:] != (height, width, 3):
             raise ValueError("adj must be (S, H=%d, W=%d, 3), got %s" % (height, width, adj.shape))
-        S = adj.shape[0]
-        dev = []
-        for name, v in (("kd", kd), ("ks", ks), ("ke", ke)):
-            if v is None:
-                dev.append(None)
-                continue
-            v = np.ascontiguousarray(np.asarray(v, np.float32))
-            if v.shape != (S, self.nT, 3):
-                raise ValueError("%s must be (S=%d, nT=%d, 3), got %s" % (name, S, self.nT, v.shape))
-            dev.append(torch.from_numpy(v).cuda())
-        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        a = torch.from_numpy(adj).cuda()
-        g = torch.zeros((S, 3, self.nT, 3), device=a.device, dtype=torch.float64)
-        ptr = [None if t is None else t.data_ptr() for t in dev]
-        N.check(N.lib().ipt_adjoint_mat_batch_dev(self.handle, C.byref(p), S, stride, ptr[0], ptr[1], ptr[2],
-                                                  a.data_ptr(), g.data_ptr(),
-                                                  torch.cuda.current_stream(a.device).cuda_stream),
-                "adjoint_materials_batch")
-        return g.cpu().numpy()
+        mats = self._materials_dev(None, kd, ks, ke, adj.shape[0])
+        return self._launch("adjoint_materials_batch", "render_materials_batch", None, mats, width, height, spp,
+                            max_bounces, seed, seed_stride, (row_begin, row_end, row_step), adj)
 
     # ---------------------------------------------------------- views (caller-supplied cameras)
     @property
@@ -364,21 +345,48 @@ class Scene:
         ``camera_bound``); works on a host-only scene too (validation only)."""
         return Views(self, cams)
 
-    def _views_dev(self, views, kd, ks, ke):
+    def _materials_dev(self, views, kd, ks, ke, n_sets=None, sets=True):
+        """(S, device copies of the kd / ks / ke host arrays; None stays None),
+        each checked against (S, nT, 3) -- S is n_sets, else the arrays' first
+        extent, 1 when all are None -- or, for one set (sets False, S None),
+        against (nT, 3)."""
         import torch
 
-        if views.scene is not self:
+        if views is not None and views.scene is not self:
             raise ValueError("the views belong to another scene")
-        dev = []
-        for name, v in (("kd", kd), ("ks", ks), ("ke", ke)):
-            if v is None:
-                dev.append(None)
-                continue
-            v = np.ascontiguousarray(np.asarray(v, np.float32))
-            if v.shape != (self.nT, 3):
-                raise ValueError("%s must be (nT=%d, 3), got %s" % (name, self.nT, v.shape))
-            dev.append(torch.from_numpy(v).cuda())
-        return torch, dev, [None if t is None else t.data_ptr() for t in dev]
+        host = [None if v is None else np.ascontiguousarray(np.asarray(v, np.float32)) for v in (kd, ks, ke)]
+        S, want, text = None, (self.nT, 3), "%s must be (nT=%d, 3), got %s"
+        if sets:
+            given = [v for v in host if v is not None]
+            S = int(n_sets) if n_sets is not None else (given[0].shape[0] if given and given[0].ndim == 3 else 1)
+            want, text = (S, self.nT, 3), "%s must be (S=%d, nT=%d, 3), got %s"
+        for name, v in zip(("kd", "ks", "ke"), host):
+            if v is not None and v.shape != want:
+                raise ValueError(text % ((name,) + want[:-1] + (v.shape,)))
+        return S, [None if v is None else torch.from_numpy(v).cuda() for v in host]
+
+    def _launch(self, what, op, views, mats, width, height, spp, max_bounces, seed, seed_stride, rows, adj=None):
+        """The launch every material and view method ends in, through the route
+        of torch_ops' `op` on torch's current stream: the render (V frames per
+        set) or, with the host array `adj`, the adjoint (3 blocks per set), as
+        a host array.  torch only provides the device memory."""
+        import torch
+
+        from . import torch_ops
+
+        route, (S, dev) = torch_ops._ROUTES[op], mats
+        p = N.make_params(width, height, spp, max_bounces, seed, *rows)
+        stride = width * height * spp if seed_stride is None else int(seed_stride)
+        lead = (max(S, 0),) if route.n_sets else ()
+        if adj is None:
+            out = torch.zeros(lead + (len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
+            symbol, tail = route.render, (out.data_ptr(),)
+        else:
+            a = torch.from_numpy(adj).cuda()
+            out = torch.zeros(lead + (3, self.nT, 3), device=a.device, dtype=torch.float64)
+            symbol, tail = route.adjoint, (a.data_ptr(), out.data_ptr())
+        torch_ops._launch(route, symbol, self, views, p, S, stride, dev, tail, out.device, what)
+        return out.cpu().numpy()
 
     def render_views(self, views, width, height, spp, max_bounces=None, seed=0, seed_stride=None, kd=None, ks=None,
                      ke=None, row_begin=0, row_end=None, row_step=1):
@@ -388,14 +396,9 @@ class Scene:
         seed_stride (default: one frame of samples, W*H*spp) and equals the
         single-camera render through its camera bit for bit.  torch only
         provides the device memory."""
-        torch, dev, ptr = self._views_dev(views, kd, ks, ke)
-        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        hdr = torch.zeros((len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
-        N.check(N.lib().ipt_render_views_dev(self.handle, views.handle, C.byref(p), stride, ptr[0], ptr[1], ptr[2],
-                                             hdr.data_ptr(), torch.cuda.current_stream(hdr.device).cuda_stream),
-                "render_views")
-        return hdr.cpu().numpy()
+        mats = self._materials_dev(views, kd, ks, ke, sets=False)
+        return self._launch("render_views", "render_views", views, mats, width, height, spp, max_bounces, seed,
+                            seed_stride, (row_begin, row_end, row_step))
 
     def adjoint_views(self, views, adj, width, height, spp, max_bounces, seed=0, seed_stride=None, kd=None, ks=None,
                       ke=None, row_begin=0, row_end=None, row_step=1):
@@ -405,31 +408,9 @@ class Scene:
         adj = np.ascontiguousarray(np.asarray(adj, np.float32))
         if adj.shape != (len(views), height, width, 3):
             raise ValueError("adj must be (V=%d, H=%d, W=%d, 3), got %s" % (len(views), height, width, adj.shape))
-        torch, dev, ptr = self._views_dev(views, kd, ks, ke)
-        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        a = torch.from_numpy(adj).cuda()
-        g = torch.zeros((3, self.nT, 3), device=a.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_views_dev(self.handle, views.handle, C.byref(p), stride, ptr[0], ptr[1], ptr[2],
-                                              a.data_ptr(), g.data_ptr(),
-                                              torch.cuda.current_stream(a.device).cuda_stream), "adjoint_views")
-        return g.cpu().numpy()
-
-    def _view_sets_dev(self, views, kd, ks, ke, n_sets):
-        """Device copies of (S, nT, 3) host arrays (None stays None) and S:
-        the arrays' shared first extent, or n_sets when all are None."""
-        import torch
-
-        if views.scene is not self:
-            raise ValueError("the views belong to another scene")
-        host = [None if v is None else np.ascontiguousarray(np.asarray(v, np.float32)) for v in (kd, ks, ke)]
-        given = [v for v in host if v is not None]
-        S = int(n_sets) if n_sets is not None else (given[0].shape[0] if given and given[0].ndim == 3 else 1)
-        for name, v in zip(("kd", "ks", "ke"), host):
-            if v is not None and v.shape != (S, self.nT, 3):
-                raise ValueError("%s must be (S=%d, nT=%d, 3), got %s" % (name, S, self.nT, v.shape))
-        dev = [None if v is None else torch.from_numpy(v).cuda() for v in host]
-        return torch, S, dev, [None if t is None else t.data_ptr() for t in dev]
+        mats = self._materials_dev(views, kd, ks, ke, sets=False)
+        return self._launch("adjoint_views", "render_views", views, mats, width, height, spp, max_bounces, seed,
+                            seed_stride, (row_begin, row_end, row_step), adj)
 
     def render_views_batch(self, views, kd=None, ks=None, ke=None, width=0, height=0, spp=1, max_bounces=4, seed=0,
                            seed_stride=None, row_begin=0, row_end=None, row_step=1, n_sets=None):
@@ -441,15 +422,9 @@ class Scene:
         ``render_views`` with set s's arrays at that seed bit for bit.
         Bounded estimator only (max_bounces 0..62).  torch only provides the
         device memory."""
-        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, n_sets)
-        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        hdr = torch.zeros((max(S, 0), len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
-        N.check(N.lib().ipt_render_views_batch_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0], ptr[1],
-                                                   ptr[2], hdr.data_ptr(),
-                                                   torch.cuda.current_stream(hdr.device).cuda_stream),
-                "render_views_batch")
-        return hdr.cpu().numpy()
+        mats = self._materials_dev(views, kd, ks, ke, n_sets)
+        return self._launch("render_views_batch", "render_views_batch", views, mats, width, height, spp, max_bounces,
+                            seed, seed_stride, (row_begin, row_end, row_step))
 
     def adjoint_views_batch(self, views, adj, kd=None, ks=None, ke=None, width=0, height=0, spp=1, max_bounces=4,
                             seed=0, seed_stride=None, row_begin=0, row_end=None, row_step=1):
@@ -462,16 +437,9 @@ class Scene:
         adj = np.ascontiguousarray(np.asarray(adj, np.float32))
         if adj.ndim != 5 or adj.shape[1:] != (len(views), height, width, 3):
             raise ValueError("adj must be (S, V=%d, H=%d, W=%d, 3), got %s" % (len(views), height, width, adj.shape))
-        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, adj.shape[0])
-        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        a = torch.from_numpy(adj).cuda()
-        g = torch.zeros((max(S, 0), 3, self.nT, 3), device=a.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_views_batch_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0], ptr[1],
-                                                    ptr[2], a.data_ptr(), g.data_ptr(),
-                                                    torch.cuda.current_stream(a.device).cuda_stream),
-                "adjoint_views_batch")
-        g = g.cpu().numpy()
+        mats = self._materials_dev(views, kd, ks, ke, adj.shape[0])
+        g = self._launch("adjoint_views_batch", "render_views_batch", views, mats, width, height, spp, max_bounces,
+                         seed, seed_stride, (row_begin, row_end, row_step), adj)
         return g[:, 0].copy(), g[:, 1].copy(), g[:, 2].copy()
 
     def render_views_batch_unbounded(self, views, kd=None, ks=None, ke=None, width=0, height=0, spp=1, seed=0,
@@ -481,15 +449,9 @@ class Scene:
         (ipt_render_views_batch_unbounded_dev).  Pair (s, b) equals view b of
         ``render_views`` at ``max_bounces=None`` with set s's arrays at seed +
         (s * V + b) * seed_stride bit for bit."""
-        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, n_sets)
-        p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        hdr = torch.zeros((max(S, 0), len(views), p.rows, width, 3), device="cuda", dtype=torch.float32)
-        N.check(N.lib().ipt_render_views_batch_unbounded_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0],
-                                                             ptr[1], ptr[2], hdr.data_ptr(),
-                                                             torch.cuda.current_stream(hdr.device).cuda_stream),
-                "render_views_batch_unbounded")
-        return hdr.cpu().numpy()
+        mats = self._materials_dev(views, kd, ks, ke, n_sets)
+        return self._launch("render_views_batch_unbounded", "render_views_batch_unbounded", views, mats, width, height,
+                            spp, None, seed, seed_stride, (row_begin, row_end, row_step))
 
     def adjoint_views_batch_unbounded(self, views, adj, kd=None, ks=None, ke=None, width=0, height=0, spp=1, seed=0,
                                       seed_stride=None, row_begin=0, row_end=None, row_step=1):
@@ -503,16 +465,9 @@ class Scene:
         adj = np.ascontiguousarray(np.asarray(adj, np.float32))
         if adj.ndim != 5 or adj.shape[1:] != (len(views), height, width, 3):
             raise ValueError("adj must be (S, V=%d, H=%d, W=%d, 3), got %s" % (len(views), height, width, adj.shape))
-        torch, S, dev, ptr = self._view_sets_dev(views, kd, ks, ke, adj.shape[0])
-        p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
-        stride = width * height * spp if seed_stride is None else int(seed_stride)
-        a = torch.from_numpy(adj).cuda()
-        g = torch.zeros((max(S, 0), 3, self.nT, 3), device=a.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_views_batch_unbounded_dev(self.handle, views.handle, C.byref(p), S, stride, ptr[0],
-                                                              ptr[1], ptr[2], a.data_ptr(), g.data_ptr(),
-                                                              torch.cuda.current_stream(a.device).cuda_stream),
-                "adjoint_views_batch_unbounded")
-        g = g.cpu().numpy()
+        mats = self._materials_dev(views, kd, ks, ke, adj.shape[0])
+        g = self._launch("adjoint_views_batch_unbounded", "render_views_batch_unbounded", views, mats, width, height,
+                         spp, None, seed, seed_stride, (row_begin, row_end, row_step), adj)
         return g[:, 0].copy(), g[:, 1].copy(), g[:, 2].copy()
 
     def view_rays(self, views, view, width, height, spp, seed, sample_index):

@@ -9,6 +9,7 @@ compute is libipt_amd.so (there is no fallback).
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -38,13 +39,19 @@ def adjoint_into(scene: Scene, params: N.Params, kd: torch.Tensor, adj_full: tor
 
 def adjoint_band(scene: Scene, params: N.Params, kd, adj_band: torch.Tensor, grad: torch.Tensor):
     """Adjoint for a launch whose adjoint image holds only its own rows."""
-    adj_band = adj_band.contiguous()
-    if params.row_step > 1:  # interleaved rows: scatter into a full-frame image
-        full = torch.zeros((params.height, params.width, 3), device=adj_band.device, dtype=torch.float32)
-        full[params.row_begin:params.row_end:params.row_step] = adj_band
-        return adjoint_into(scene, params, kd, full.data_ptr(), grad)
-    base = adj_band.data_ptr() - params.row_begin * params.width * 3 * 4  # global-pixel indexing
+    base, frame = _adjoint_base(adj_band.contiguous(), params)  # frame: referenced until the call has returned
     return adjoint_into(scene, params, kd, base, grad)
+
+
+def _adjoint_base(adj: torch.Tensor, p: N.Params):
+    """(pointer, its tensor): the launch's own rows `adj` (contiguous float32)
+    as the adjoint kernels want them, indexed by global pixel.  The caller
+    keeps the tensor until the native call has returned."""
+    if p.row_step > 1:  # interleaved rows: scatter into a full-frame image
+        full = torch.zeros((p.height, p.width, 3), device=adj.device, dtype=torch.float32)
+        full[p.row_begin:p.row_end:p.row_step] = adj
+        return full.data_ptr(), full
+    return adj.data_ptr() - p.row_begin * p.width * 3 * 4, adj  # a full frame (row_begin 0): adj itself
 
 
 class _RenderFn(torch.autograd.Function):
@@ -104,38 +111,113 @@ BATCH_REFUSED = ("material adjoint: the scene batch (n_scenes > 1) is not suppor
                  "pass (S, nT, 3) tensors to render_materials_batch")
 
 
+class _Route(NamedTuple):
+    """How one public material op reaches the library: its two symbols, which
+    of (views handle, n_sets, seed_stride) the launches take after the scene
+    and the params, and its refusals.  N.check's `what` is the symbol."""
+
+    name: str
+    render: str
+    adjoint: str
+    views: bool = False
+    n_sets: bool = False
+    seed_stride: bool = False
+    ldr: bool = False  # the render takes a trailing ldr pointer (the one-set material render alone)
+    set_refused: Optional[str] = None  # one-set ops: the NativeError for an (S, nT, 3) tensor (None: a shape like any)
+    unbounded_refused: Optional[str] = None  # bounded ops: the NativeError for no bounce cap
+
+
+_MAT = _Route(
+    "render_materials", "ipt_render_mat_dev", "ipt_adjoint_mat_dev", ldr=True, set_refused=BATCH_REFUSED,
+    unbounded_refused="material adjoint: the unbounded estimator (max_bounces < 0) is not supported by "
+                      "render_materials; give max_bounces in 0..62 or call render_materials_unbounded")
+_ROUTES = {r.name: r for r in (
+    _MAT,
+    _MAT._replace(name="render_materials_unbounded", adjoint="ipt_adjoint_mat_unbounded_dev", unbounded_refused=None,
+                  set_refused="unbounded material adjoint: the scene batch (n_scenes > 1) is not supported"),
+    _Route("render_materials_batch", "ipt_render_mat_batch_dev", "ipt_adjoint_mat_batch_dev", n_sets=True,
+           seed_stride=True,
+           unbounded_refused="material adjoint: the unbounded estimator (max_bounces < 0) is not supported by the "
+                             "scene batch; give max_bounces in 0..62 (one set: render_materials_unbounded)"),
+    _Route("render_views", "ipt_render_views_dev", "ipt_adjoint_views_dev", views=True, seed_stride=True,
+           unbounded_refused="views adjoint: the unbounded estimator (max_bounces < 0) is not supported by "
+                             "render_views; give max_bounces in 0..62"),
+    _Route("render_views_batch", "ipt_render_views_batch_dev", "ipt_adjoint_views_batch_dev", views=True, n_sets=True,
+           seed_stride=True,
+           unbounded_refused="views batch: the unbounded estimator (max_bounces < 0) is not supported by "
+                             "render_views_batch; give max_bounces in 0..62"),
+    _Route("render_views_batch_unbounded", "ipt_render_views_batch_unbounded_dev",
+           "ipt_adjoint_views_batch_unbounded_dev", views=True, n_sets=True, seed_stride=True),
+)}
+
+
 def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-class _RenderMaterialsFn(torch.autograd.Function):
+def _launch(route: _Route, symbol: str, scene, views, params: N.Params, n_sets, stride, mats, tail, device,
+            what=None):
+    """One native call of `route` on torch's current stream: the scene, the
+    arguments the route takes, the three material pointers, then `tail`."""
+    args = [scene.handle] + ([views.handle] if route.views else []) + [C.byref(params)]
+    args += ([n_sets] if route.n_sets else []) + ([stride] if route.seed_stride else [])
+    N.check(getattr(N.lib(), symbol)(*args, *[_ptr(t) for t in mats], *tail, _stream(device)), what or symbol)
+
+
+def _validate(route: _Route, scene, mats, max_bounces):
+    given = [t for t in mats if t is not None]
+    if not given:
+        raise ValueError("%s needs at least one of kd, ks, ke as a device tensor" % route.name)
+    for t in given:
+        if route.n_sets:
+            if t.dim() != 3 or tuple(t.shape[1:]) != (scene.nT, 3):
+                raise ValueError("kd, ks, ke must be (S, nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+            if t.shape[0] != given[0].shape[0]:
+                raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
+                                 [tuple(u.shape) for u in given])
+            continue
+        if route.set_refused and t.dim() == 3:
+            raise N.NativeError(route.set_refused)
+        if tuple(t.shape) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+    if route.unbounded_refused and (max_bounces is None or max_bounces < 0):
+        raise N.NativeError(route.unbounded_refused)
+
+
+class _MaterialsFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, kd, ks, ke, scene, params, adjoint_seed):
-        dev = next(t for t in (kd, ks, ke) if t is not None).device
+    def forward(ctx, kd, ks, ke, route, scene, views, params, stride, adjoint_seed):
+        first = next(t for t in (kd, ks, ke) if t is not None)
+        lead = ((first.shape[0],) if route.n_sets else ()) + ((len(views),) if route.views else ())
         c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
-        hdr = torch.empty((params.rows, params.width, 3), device=dev, dtype=torch.float32)
-        N.check(N.lib().ipt_render_mat_dev(scene.handle, C.byref(params), _ptr(c[0]), _ptr(c[1]), _ptr(c[2]),
-                                           hdr.data_ptr(), None, _stream(dev)), "ipt_render_mat_dev")
-        ctx.scene, ctx.params, ctx.adjoint_seed, ctx.mat = scene, params, adjoint_seed, c
+        hdr = torch.empty(lead + (params.rows, params.width, 3), device=first.device, dtype=torch.float32)
+        _launch(route, route.render, scene, views, params, lead[0] if route.n_sets else None, stride, c,
+                (hdr.data_ptr(),) + ((None,) if route.ldr else ()), first.device)
+        ctx.call, ctx.adjoint_seed, ctx.mat = (route, scene, views, params, lead, stride), adjoint_seed, c
         return hdr
 
     @staticmethod
     def backward(ctx, grad_hdr):
-        p = _replay_params(ctx.params, ctx.adjoint_seed)
-        kd, ks, ke = ctx.mat
-        adj = grad_hdr.float().contiguous()
-        g = torch.zeros((3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
-        if p.row_step > 1:  # interleaved rows: scatter into a full-frame image (as adjoint_band)
-            full = torch.zeros((p.height, p.width, 3), device=adj.device, dtype=torch.float32)
-            full[p.row_begin:p.row_end:p.row_step] = adj
-            base = full.data_ptr()
-        else:
-            base = adj.data_ptr() - p.row_begin * p.width * 3 * 4  # global-pixel indexing
-        N.check(N.lib().ipt_adjoint_mat_dev(ctx.scene.handle, C.byref(p), _ptr(kd), _ptr(ks), _ptr(ke), base,
-                                            g.data_ptr(), _stream(adj.device)), "ipt_adjoint_mat_dev")
-        out = [g[i].float() if (t is not None and ctx.needs_input_grad[i]) else None
-               for i, t in enumerate((kd, ks, ke))]
-        return out[0], out[1], out[2], None, None, None
+        route, scene, views, params, lead, stride = ctx.call
+        p = _replay_params(params, ctx.adjoint_seed)
+        sets = lead[:1] if route.n_sets else ()
+        g = torch.zeros(sets + (3, scene.nT, 3), device=grad_hdr.device, dtype=torch.float64)
+        base, frame = _adjoint_base(grad_hdr.float().contiguous(), p)  # frame: referenced until the call has returned
+        _launch(route, route.adjoint, scene, views, p, sets[0] if sets else None, stride, ctx.mat,
+                (base, g.data_ptr()), grad_hdr.device)
+        out = [g.select(-3, i).float() if (t is not None and ctx.needs_input_grad[i]) else None
+               for i, t in enumerate(ctx.mat)]
+        return out[0], out[1], out[2], None, None, None, None, None, None
+
+
+def _materials(name, scene, views, kd, ks, ke, width, height, spp, max_bounces, seed, seed_stride, adjoint_seed,
+               rows=(0, None, 1)):
+    """The public material ops: validate, then _MaterialsFn on the op's route."""
+    route = _ROUTES[name]
+    _validate(route, scene, (kd, ks, ke), max_bounces)
+    stride = width * height * spp if seed_stride is None else int(seed_stride)
+    p = N.make_params(width, height, spp, max_bounces, seed, *rows)
+    return _MaterialsFn.apply(kd, ks, ke, route, scene, views, p, stride, adjoint_seed)
 
 
 def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4, seed: int = 0,
@@ -151,43 +233,8 @@ def render_materials(scene: Scene, kd, ks, ke, width: int, height: int, spp: int
     ``render_materials_unbounded`` takes, and batched inputs (S, nT, 3),
     which ``render_materials_batch`` takes.
     `adjoint_seed` as in ``render``."""
-    given = [t for t in (kd, ks, ke) if t is not None]
-    if not given:
-        raise ValueError("render_materials needs at least one of kd, ks, ke as a device tensor")
-    for t in given:
-        if t.dim() == 3:
-            raise N.NativeError(BATCH_REFUSED)
-        if tuple(t.shape) != (scene.nT, 3):
-            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
-    if max_bounces is None or max_bounces < 0:
-        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported by "
-                            "render_materials; give max_bounces in 0..62 or call render_materials_unbounded")
-    p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
-    return _RenderMaterialsFn.apply(kd, ks, ke, scene, p, adjoint_seed)
-
-
-class _RenderMaterialsUnboundedFn(_RenderMaterialsFn):
-    """_RenderMaterialsFn at max_bounces = -1: the same forward
-    (ipt_render_mat_dev), the backward through ipt_adjoint_mat_unbounded_dev."""
-
-    @staticmethod
-    def backward(ctx, grad_hdr):
-        p = _replay_params(ctx.params, ctx.adjoint_seed)
-        kd, ks, ke = ctx.mat
-        adj = grad_hdr.float().contiguous()
-        g = torch.zeros((3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
-        if p.row_step > 1:  # interleaved rows: scatter into a full-frame image (as adjoint_band)
-            full = torch.zeros((p.height, p.width, 3), device=adj.device, dtype=torch.float32)
-            full[p.row_begin:p.row_end:p.row_step] = adj
-            base = full.data_ptr()
-        else:
-            base = adj.data_ptr() - p.row_begin * p.width * 3 * 4  # global-pixel indexing
-        N.check(N.lib().ipt_adjoint_mat_unbounded_dev(ctx.scene.handle, C.byref(p), _ptr(kd), _ptr(ks), _ptr(ke),
-                                                      base, g.data_ptr(), _stream(adj.device)),
-                "ipt_adjoint_mat_unbounded_dev")
-        out = [g[i].float() if (t is not None and ctx.needs_input_grad[i]) else None
-               for i, t in enumerate((kd, ks, ke))]
-        return out[0], out[1], out[2], None, None, None
+    return _materials("render_materials", scene, None, kd, ks, ke, width, height, spp, max_bounces, seed, None,
+                      adjoint_seed, (row_begin, row_end, row_step))
 
 
 def render_materials_unbounded(scene: Scene, kd, ks, ke, width: int, height: int, spp: int, seed: int = 0,
@@ -200,43 +247,8 @@ def render_materials_unbounded(scene: Scene, kd, ks, ke, width: int, height: int
     dL/dKs and dL/dKe).  kd, ks, ke, the masks, None and
     no-grad inputs and `adjoint_seed` as in ``render_materials``; batched
     (S, nT, 3) inputs are refused (NativeError)."""
-    given = [t for t in (kd, ks, ke) if t is not None]
-    if not given:
-        raise ValueError("render_materials_unbounded needs at least one of kd, ks, ke as a device tensor")
-    for t in given:
-        if t.dim() == 3:
-            raise N.NativeError("unbounded material adjoint: the scene batch (n_scenes > 1) is not supported")
-        if tuple(t.shape) != (scene.nT, 3):
-            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
-    p = N.make_params(width, height, spp, None, seed, row_begin, row_end, row_step)
-    return _RenderMaterialsUnboundedFn.apply(kd, ks, ke, scene, p, adjoint_seed)
-
-
-class _RenderMaterialsBatchFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, kd, ks, ke, scene, params, stride, adjoint_seed):
-        given = [t for t in (kd, ks, ke) if t is not None]
-        dev, S = given[0].device, given[0].shape[0]
-        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
-        hdr = torch.empty((S, params.height, params.width, 3), device=dev, dtype=torch.float32)
-        N.check(N.lib().ipt_render_mat_batch_dev(scene.handle, C.byref(params), S, stride, _ptr(c[0]), _ptr(c[1]),
-                                                 _ptr(c[2]), hdr.data_ptr(), _stream(dev)),
-                "ipt_render_mat_batch_dev")
-        ctx.scene, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat, ctx.S = scene, params, stride, adjoint_seed, c, S
-        return hdr
-
-    @staticmethod
-    def backward(ctx, grad_hdr):
-        p = _replay_params(ctx.params, ctx.adjoint_seed)
-        kd, ks, ke = ctx.mat
-        adj = grad_hdr.float().contiguous()
-        g = torch.zeros((ctx.S, 3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_mat_batch_dev(ctx.scene.handle, C.byref(p), ctx.S, ctx.stride, _ptr(kd), _ptr(ks),
-                                                  _ptr(ke), adj.data_ptr(), g.data_ptr(), _stream(adj.device)),
-                "ipt_adjoint_mat_batch_dev")
-        out = [g[:, i].float() if (t is not None and ctx.needs_input_grad[i]) else None
-               for i, t in enumerate((kd, ks, ke))]
-        return out[0], out[1], out[2], None, None, None, None
+    return _materials("render_materials_unbounded", scene, None, kd, ks, ke, width, height, spp, None, seed, None,
+                      adjoint_seed, (row_begin, row_end, row_step))
 
 
 def render_materials_batch(scene: Scene, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4,
@@ -250,21 +262,8 @@ def render_materials_batch(scene: Scene, kd, ks, ke, width: int, height: int, sp
     ``seed + b * seed_stride`` bit for bit (default stride: one frame of
     samples, as ``render_batch``).  Masks, refusals and `adjoint_seed` as in
     ``render_materials``."""
-    given = [t for t in (kd, ks, ke) if t is not None]
-    if not given:
-        raise ValueError("render_materials_batch needs at least one of kd, ks, ke as a device tensor")
-    for t in given:
-        if t.dim() != 3 or tuple(t.shape[1:]) != (scene.nT, 3):
-            raise ValueError("kd, ks, ke must be (S, nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
-        if t.shape[0] != given[0].shape[0]:
-            raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
-                             [tuple(u.shape) for u in given])
-    if max_bounces is None or max_bounces < 0:
-        raise N.NativeError("material adjoint: the unbounded estimator (max_bounces < 0) is not supported by the "
-                            "scene batch; give max_bounces in 0..62 (one set: render_materials_unbounded)")
-    stride = width * height * spp if seed_stride is None else int(seed_stride)
-    p = N.make_params(width, height, spp, max_bounces, seed)
-    return _RenderMaterialsBatchFn.apply(kd, ks, ke, scene, p, stride, adjoint_seed)
+    return _materials("render_materials_batch", scene, None, kd, ks, ke, width, height, spp, max_bounces, seed,
+                      seed_stride, adjoint_seed)
 
 
 class _BatchRenderFn(torch.autograd.Function):
@@ -305,34 +304,6 @@ def render_batch(scene: Scene, kd: torch.Tensor, width: int, height: int, spp: i
     return _BatchRenderFn.apply(kd, scene, p, stride, adjoint_seed)
 
 
-class _RenderViewsFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, kd, ks, ke, scene, views, params, stride, adjoint_seed):
-        given = [t for t in (kd, ks, ke) if t is not None]
-        dev = given[0].device
-        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
-        hdr = torch.empty((len(views), params.height, params.width, 3), device=dev, dtype=torch.float32)
-        N.check(N.lib().ipt_render_views_dev(scene.handle, views.handle, C.byref(params), stride, _ptr(c[0]),
-                                             _ptr(c[1]), _ptr(c[2]), hdr.data_ptr(), _stream(dev)),
-                "ipt_render_views_dev")
-        ctx.scene, ctx.views, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat = (scene, views, params, stride,
-                                                                                  adjoint_seed, c)
-        return hdr
-
-    @staticmethod
-    def backward(ctx, grad_hdr):
-        p = _replay_params(ctx.params, ctx.adjoint_seed)
-        kd, ks, ke = ctx.mat
-        adj = grad_hdr.float().contiguous()
-        g = torch.zeros((3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_views_dev(ctx.scene.handle, ctx.views.handle, C.byref(p), ctx.stride, _ptr(kd),
-                                              _ptr(ks), _ptr(ke), adj.data_ptr(), g.data_ptr(), _stream(adj.device)),
-                "ipt_adjoint_views_dev")
-        out = [g[i].float() if (t is not None and ctx.needs_input_grad[i]) else None
-               for i, t in enumerate((kd, ks, ke))]
-        return out[0], out[1], out[2], None, None, None, None, None
-
-
 def render_views(scene: Scene, views, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4, seed: int = 0,
                  seed_stride=None, adjoint_seed=None) -> torch.Tensor:
     """``render_materials`` through V caller-supplied cameras (``scene.views``)
@@ -344,46 +315,8 @@ def render_views(scene: Scene, views, kd, ks, ke, width: int, height: int, spp: 
     is ONE launch of the views' material adjoint, the gradient summed over the
     views, returned as float32 for the inputs that require it.  Bounded
     estimator only (max_bounces 0..62).  `adjoint_seed` as in ``render``."""
-    given = [t for t in (kd, ks, ke) if t is not None]
-    if not given:
-        raise ValueError("render_views needs at least one of kd, ks, ke as a device tensor")
-    for t in given:
-        if tuple(t.shape) != (scene.nT, 3):
-            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
-    if max_bounces is None or max_bounces < 0:
-        raise N.NativeError("views adjoint: the unbounded estimator (max_bounces < 0) is not supported by "
-                            "render_views; give max_bounces in 0..62")
-    stride = width * height * spp if seed_stride is None else int(seed_stride)
-    p = N.make_params(width, height, spp, max_bounces, seed)
-    return _RenderViewsFn.apply(kd, ks, ke, scene, views, p, stride, adjoint_seed)
-
-
-class _RenderViewsBatchFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, kd, ks, ke, scene, views, params, stride, adjoint_seed):
-        given = [t for t in (kd, ks, ke) if t is not None]
-        dev, S = given[0].device, given[0].shape[0]
-        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
-        hdr = torch.empty((S, len(views), params.height, params.width, 3), device=dev, dtype=torch.float32)
-        N.check(N.lib().ipt_render_views_batch_dev(scene.handle, views.handle, C.byref(params), S, stride, _ptr(c[0]),
-                                                   _ptr(c[1]), _ptr(c[2]), hdr.data_ptr(), _stream(dev)),
-                "ipt_render_views_batch_dev")
-        ctx.scene, ctx.views, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat, ctx.S = (scene, views, params, stride,
-                                                                                         adjoint_seed, c, S)
-        return hdr
-
-    @staticmethod
-    def backward(ctx, grad_hdr):
-        p = _replay_params(ctx.params, ctx.adjoint_seed)
-        kd, ks, ke = ctx.mat
-        adj = grad_hdr.float().contiguous()
-        g = torch.zeros((ctx.S, 3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_views_batch_dev(ctx.scene.handle, ctx.views.handle, C.byref(p), ctx.S, ctx.stride,
-                                                    _ptr(kd), _ptr(ks), _ptr(ke), adj.data_ptr(), g.data_ptr(),
-                                                    _stream(adj.device)), "ipt_adjoint_views_batch_dev")
-        out = [g[:, i].float() if (t is not None and ctx.needs_input_grad[i]) else None
-               for i, t in enumerate((kd, ks, ke))]
-        return out[0], out[1], out[2], None, None, None, None, None
+    return _materials("render_views", scene, views, kd, ks, ke, width, height, spp, max_bounces, seed, seed_stride,
+                      adjoint_seed)
 
 
 def render_views_batch(scene: Scene, views, kd, ks, ke, width: int, height: int, spp: int, max_bounces=4,
@@ -398,50 +331,8 @@ def render_views_batch(scene: Scene, views, kd, ks, ke, width: int, height: int,
     S * V pairs, each set's gradient summed over its views, returned as
     float32 for the inputs that require it.  Bounded estimator only
     (max_bounces 0..62).  `adjoint_seed` as in ``render_views``."""
-    given = [t for t in (kd, ks, ke) if t is not None]
-    if not given:
-        raise ValueError("render_views_batch needs at least one of kd, ks, ke as a device tensor")
-    for t in given:
-        if t.dim() != 3 or tuple(t.shape[1:]) != (scene.nT, 3):
-            raise ValueError("kd, ks, ke must be (S, nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
-        if t.shape[0] != given[0].shape[0]:
-            raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
-                             [tuple(u.shape) for u in given])
-    if max_bounces is None or max_bounces < 0:
-        raise N.NativeError("views batch: the unbounded estimator (max_bounces < 0) is not supported by "
-                            "render_views_batch; give max_bounces in 0..62")
-    stride = width * height * spp if seed_stride is None else int(seed_stride)
-    p = N.make_params(width, height, spp, max_bounces, seed)
-    return _RenderViewsBatchFn.apply(kd, ks, ke, scene, views, p, stride, adjoint_seed)
-
-
-class _RenderViewsBatchUnboundedFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, kd, ks, ke, scene, views, params, stride, adjoint_seed):
-        given = [t for t in (kd, ks, ke) if t is not None]
-        dev, S = given[0].device, given[0].shape[0]
-        c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke)]
-        hdr = torch.empty((S, len(views), params.height, params.width, 3), device=dev, dtype=torch.float32)
-        N.check(N.lib().ipt_render_views_batch_unbounded_dev(scene.handle, views.handle, C.byref(params), S, stride,
-                                                             _ptr(c[0]), _ptr(c[1]), _ptr(c[2]), hdr.data_ptr(),
-                                                             _stream(dev)), "ipt_render_views_batch_unbounded_dev")
-        ctx.scene, ctx.views, ctx.params, ctx.stride, ctx.adjoint_seed, ctx.mat, ctx.S = (scene, views, params, stride,
-                                                                                         adjoint_seed, c, S)
-        return hdr
-
-    @staticmethod
-    def backward(ctx, grad_hdr):
-        p = _replay_params(ctx.params, ctx.adjoint_seed)
-        kd, ks, ke = ctx.mat
-        adj = grad_hdr.float().contiguous()
-        g = torch.zeros((ctx.S, 3, ctx.scene.nT, 3), device=adj.device, dtype=torch.float64)
-        N.check(N.lib().ipt_adjoint_views_batch_unbounded_dev(ctx.scene.handle, ctx.views.handle, C.byref(p), ctx.S,
-                                                              ctx.stride, _ptr(kd), _ptr(ks), _ptr(ke), adj.data_ptr(),
-                                                              g.data_ptr(), _stream(adj.device)),
-                "ipt_adjoint_views_batch_unbounded_dev")
-        out = [g[:, i].float() if (t is not None and ctx.needs_input_grad[i]) else None
-               for i, t in enumerate((kd, ks, ke))]
-        return out[0], out[1], out[2], None, None, None, None, None
+    return _materials("render_views_batch", scene, views, kd, ks, ke, width, height, spp, max_bounces, seed,
+                      seed_stride, adjoint_seed)
 
 
 def render_views_batch_unbounded(scene: Scene, views, kd, ks, ke, width: int, height: int, spp: int, seed: int = 0,
@@ -454,15 +345,5 @@ def render_views_batch_unbounded(scene: Scene, views, kd, ks, ke, width: int, he
     (ipt_adjoint_views_batch_unbounded_dev), float32 gradients
     for the inputs that require them, None for the others.  Seeds, masks and
     `adjoint_seed` as in ``render_views_batch``."""
-    given = [t for t in (kd, ks, ke) if t is not None]
-    if not given:
-        raise ValueError("render_views_batch_unbounded needs at least one of kd, ks, ke as a device tensor")
-    for t in given:
-        if t.dim() != 3 or tuple(t.shape[1:]) != (scene.nT, 3):
-            raise ValueError("kd, ks, ke must be (S, nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
-        if t.shape[0] != given[0].shape[0]:
-            raise ValueError("kd, ks, ke must hold the same number of sets, got %s" %
-                             [tuple(u.shape) for u in given])
-    stride = width * height * spp if seed_stride is None else int(seed_stride)
-    p = N.make_params(width, height, spp, None, seed)
-    return _RenderViewsBatchUnboundedFn.apply(kd, ks, ke, scene, views, p, stride, adjoint_seed)
+    return _materials("render_views_batch_unbounded", scene, views, kd, ks, ke, width, height, spp, None, seed,
+                      seed_stride, adjoint_seed)

@@ -347,6 +347,30 @@ def test_torch_op(A, oracle):
                                rtol=1e-6, atol=1e-30)
 
 
+@pytest.mark.parametrize("band", [(2, 8, 2), (3, 7, 1)], ids=["rows-2-4-6", "rows-3-to-6"])
+def test_torch_op_band_with_adjoint_seed(band):
+    """A band of interleaved rows (scattered into a full frame) and a band of consecutive rows (the band's
+    pointer moved back by row_begin rows), each with the backward on a stream of its own: the op's gradient
+    is the host method's at that seed and band (two launches of one adjoint: test_torch_op's bound)."""
+    from inverse_path_tracer_amd import torch_ops
+    from inverse_path_tracer_amd.scene import Scene
+
+    P = Scene.from_file(os.path.join(ASSETS, "phong", "scene0_phong.txt"))
+    W, H, spp, mb, seed, aseed = 8, 8, 4, 2, 6, 6 + 8 * 8 * 4
+    rb, re_, rs = band
+    kd0, ks0, ke0, _ = P.material_params()
+    kd, ks, ke = (torch.tensor(v, device="cuda", requires_grad=True) for v in (kd0, ks0, ke0))
+    img = torch_ops.render_materials(P, kd, ks, ke, W, H, spp, mb, seed, rb, re_, adjoint_seed=aseed, row_step=rs)
+    assert np.array_equal(bits(img.detach().cpu().numpy()), bits(P.render(W, H, spp, mb, seed)[rb:re_:rs]))
+    adj = pos_adj(W, H, 3)
+    (img * torch.tensor(adj[rb:re_:rs], device="cuda")).sum().backward()
+    want = P.adjoint_materials(adj, W, H, spp, mb, aseed, rb, re_, rs)
+    for t, g in zip((kd, ks, ke), want):
+        assert np.any(g != 0)
+        np.testing.assert_allclose(t.grad.cpu().numpy(), g, rtol=1e-6, atol=1e-30)
+    P.close()
+
+
 # ------------------------------------------------------------- 7. recovery
 def test_recovery_of_cube_ks_and_light_ke():
     from inverse_path_tracer_amd import torch_ops

@@ -388,6 +388,30 @@ def test_torch_op(A):
         torch_ops.render_materials_batch(P, kd[0], None, None, W, H, spp, mb, seed)
 
 
+def test_torch_op_adjoint_seed():
+    """The backward on a stream of its own, one input None and one without a gradient: the op's gradient is
+    the host method's at that seed (two launches of one adjoint: test_torch_op's bound)."""
+    from inverse_path_tracer_amd import torch_ops
+    from inverse_path_tracer_amd.scene import Scene
+
+    P = Scene.from_file(os.path.join(ASSETS, "phong", "scene0_phong.txt"))
+    W, H, spp, mb, seed, aseed, S = 8, 8, 4, 2, 6, 12345, 2
+    _, ks0, ke0, _ = P.material_params()
+    ks0 = np.stack([ks0, 0.5 * ks0])
+    ke0 = np.stack([ke0, 2 * ke0])
+    ks = torch.tensor(ks0, device="cuda", requires_grad=True)
+    img = torch_ops.render_materials_batch(P, None, ks, torch.tensor(ke0, device="cuda"), W, H, spp, mb, seed,
+                                           adjoint_seed=aseed)
+    adj = pos_adj(S, W, H, 3)
+    (img * torch.tensor(adj, device="cuda")).sum().backward()
+    want = P.adjoint_materials_batch(adj, None, ks0, ke0, W, H, spp, mb, aseed)
+    assert np.any(want[0, 1] != 0) and np.any(want[1, 1] != 0)
+    np.testing.assert_allclose(ks.grad.cpu().numpy(), want[:, 1], rtol=1e-6, atol=1e-30)
+    assert not np.allclose(ks.grad.cpu().numpy(), P.adjoint_materials_batch(adj, None, ks0, ke0, W, H, spp, mb,
+                                                                             seed)[:, 1], rtol=1e-6, atol=1e-30)
+    P.close()
+
+
 # ------------------------------------------------------------- refusals
 def test_refusals_leave_the_stream_usable(A):
     from inverse_path_tracer_amd import NativeError, torch_ops

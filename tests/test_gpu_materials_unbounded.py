@@ -20,11 +20,12 @@ own unbounded Kd adjoint by tools/matgrad_calibrate_unbounded.py (its figures
 are written beside the constants, the bars are 8x them).
 """
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
-from conftest import SCENE0, SPHERE_OBJ, product_scene
+from conftest import ASSETS, SCENE0, SPHERE_OBJ, product_scene
 from test_gpu_materials import (bits, dot64, g9, oracle_hdr, phong_mtl, pos_adj, scene_a, scene_b, stencil)
 
 pytestmark = pytest.mark.gpu
@@ -360,6 +361,31 @@ def test_torch_op(A, oracle):
     np.testing.assert_allclose(ke4.grad.cpu().numpy(),
                                P.adjoint_materials_unbounded(adj.cpu().numpy(), W, H, spp, seed + W * H * spp)[2],
                                rtol=1e-6, atol=1e-30)
+
+
+@pytest.mark.parametrize("band", [(2, 8, 2), (3, 7, 1)], ids=["rows-2-4-6", "rows-3-to-6"])
+def test_torch_op_band_with_adjoint_seed(band):
+    """A band of interleaved rows (scattered into a full frame) and a band of consecutive rows (the band's
+    pointer moved back by row_begin rows), each with the backward on a stream of its own: the op's gradient
+    is the host method's at that seed and band (two launches of one adjoint: test_torch_op's bound)."""
+    from inverse_path_tracer_amd import torch_ops
+    from inverse_path_tracer_amd.scene import Scene
+
+    P = Scene.from_file(os.path.join(ASSETS, "phong", "scene0_phong.txt"))
+    W, H, spp, seed, aseed = 8, 8, 4, 6, 6 + 8 * 8 * 4
+    rb, re_, rs = band
+    kd0, ks0, ke0, _ = P.material_params()
+    kd, ks, ke = (torch.tensor(v, device="cuda", requires_grad=True) for v in (kd0, ks0, ke0))
+    img = torch_ops.render_materials_unbounded(P, kd, ks, ke, W, H, spp, seed, rb, re_, adjoint_seed=aseed,
+                                               row_step=rs)
+    assert np.array_equal(bits(img.detach().cpu().numpy()), bits(P.render(W, H, spp, None, seed)[rb:re_:rs]))
+    adj = pos_adj(W, H, 3)
+    (img * torch.tensor(adj[rb:re_:rs], device="cuda")).sum().backward()
+    want = P.adjoint_materials_unbounded(adj, W, H, spp, aseed, rb, re_, rs)
+    for t, g in zip((kd, ks, ke), want):
+        assert np.any(g != 0)
+        np.testing.assert_allclose(t.grad.cpu().numpy(), g, rtol=1e-6, atol=1e-30)
+    P.close()
 
 
 # ------------------------------------------------------------- 7. recovery
