@@ -91,6 +91,10 @@ int ipt_selftest_math(uint64_t n, uint64_t seed, uint64_t *counts);
  * unaffected (the counters reset themselves on the device).  No reference
  * counterpart. */
 void ipt_debug_fail_launches(int n);
+/* Diagnostic (tests): the number of trace launches since the library was
+ * loaded that read a small scene's shading data from the LDS tables (the
+ * trace_shade_kernel instances).  No reference counterpart. */
+int ipt_debug_shade_launches(void);
 /* Diagnostic (tests): the unbounded adjoint's record ring at reduced sizes --
  * pool_chunks 16-slot chunks per wave pool (1..63) and lds_slots LDS slots
  * per lane (>= 1); 0 restores the launch's own choice.  Small pools make

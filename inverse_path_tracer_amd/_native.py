@@ -79,6 +79,7 @@ SIGNATURES = {
     "ipt_device_count": (C.c_int, []),
     "ipt_selftest_math": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ipt_debug_fail_launches": (None, [C.c_int]),
+    "ipt_debug_shade_launches": (C.c_int, []),
     "ipt_debug_adju_ring": (None, [C.c_int, C.c_int]),
     "ipt_legacy_config": (None, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
     "ipt_load_scene": (C.c_int, [C.c_int, fp, fp, fp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(vp)]),

@@ -100,6 +100,7 @@ int ipt_selftest_math(uint64_t n, uint64_t seed, uint64_t *counts) {
   return gpu_status(ipt::gpu_selftest_math(n, seed, counts));
 }
 void ipt_debug_fail_launches(int n) { ipt::gpu_debug_fail_launches(n); }
+int ipt_debug_shade_launches(void) { return ipt::gpu_debug_shade_launches(); }
 void ipt_debug_adju_ring(int pool_chunks, int lds_slots) { ipt::gpu_debug_adju_ring(pool_chunks, lds_slots); }
 
 void ipt_legacy_config(int width, int height, int spp, int max_bounces, int64_t seed) {

@@ -1419,6 +1419,31 @@ __device__ __forceinline__ V3 shading_normal(const TriGeom &g, V3 q) {
   return unit(n);
 }
 
+// Word f of a triangle's TriShade / an emitter's EmitShade record
+// (scene_layout.h): the bit patterns of the fields they copy.  gw: the
+// triangle's TriGeom as words; mw: its TriMat as words, nullptr for record nT
+// (the camera's rotation has no material).
+__device__ __forceinline__ uint32_t shade_flags_word(const uint32_t *gw, const uint32_t *mw) {
+  return gw[offsetof(TriGeom, flags) / 4] | (mw ? mw[offsetof(TriMat, flags) / 4] << 8 : 0u);
+}
+__device__ __forceinline__ uint32_t tri_shade_word(const uint32_t *gw, const uint32_t *mw, int f) {
+  if (f < TS_FLAGS) return gw[offsetof(TriGeom, vn) / 4 + f - TS_VN];
+  if (f == TS_FLAGS) return shade_flags_word(gw, mw);
+  if (f < TS_KE) return gw[offsetof(TriGeom, R) / 4 + f - TS_R];
+  return mw ? mw[offsetof(TriMat, ke) / 4 + f - TS_KE] : 0u;
+}
+__device__ __forceinline__ uint32_t emit_shade_word(const uint32_t *gw, const uint32_t *mw, int tri, float pmf, double pmfr,
+                                                    int f) {
+  if (f == ES_TRI) return (uint32_t)tri;
+  if (f < ES_VN) return gw[offsetof(TriGeom, v) / 4 + f - ES_V];
+  if (f < ES_FLAGS) return gw[offsetof(TriGeom, vn) / 4 + f - ES_VN];
+  if (f == ES_FLAGS) return shade_flags_word(gw, mw);
+  if (f < ES_PMF) return mw[offsetof(TriMat, ke) / 4 + f - ES_KE];
+  if (f == ES_PMF) return __float_as_uint(pmf);
+  const uint64_t b = (uint64_t)__double_as_longlong(pmfr);
+  return f == ES_PMFR ? (uint32_t)b : (uint32_t)(b >> 32);
+}
+
 // Camera ray (path_trace.cu:155-165) + Ray::transform (scene_basics.h:307-319)
 // rcW / rcH: 1/W and 1/H when W and H are powers of two (then x * rcW == x / W
 // exactly: a power-of-two scale of a normal float), else 0 (divide).

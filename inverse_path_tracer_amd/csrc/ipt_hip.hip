@@ -54,6 +54,10 @@ const char *gpu_last_error() { return g_gpu_err.c_str(); }
 // nothing behind that a later launch on the stream depends on
 static std::atomic<int> g_fail_launches{0};
 void gpu_debug_fail_launches(int n) { g_fail_launches.store(n > 0 ? n : 0); }
+// ipt_debug_shade_launches(): trace launches since the library was loaded that
+// ran a trace_shade_kernel instance (the shading tables in LDS)
+static std::atomic<int> g_shade_launches{0};
+int gpu_debug_shade_launches() { return g_shade_launches.load(); }
 // ipt_debug_adju_ring(chunks, slots): the unbounded adjoint's pool chunks per
 // wave and LDS slots per lane forced small (0: the launch's choice) -- the
 // tests' way to run the empty-pool and short-ring paths
@@ -261,7 +265,7 @@ struct TraceArgs {
   int sample_major;  // FWD: sample buffer [s][pixel][3] (else [pixel][s][3])
   int kd_tables;     // kd and kd/pi staged in LDS
   const float *kdpi_g;  // kd/pi in global memory (large scenes: no LDS tables), per launch
-  int small_pairs;   // nT <= 2*kSmallPairs: unrolled closest-hit, plane offsets in LDS
+  int small_pairs;   // bit 0: nT <= 2*kSmallPairs: unrolled closest-hit, plane offsets in LDS; bit 1 (kSmallShade): the shading tables too
   uint64_t npix;     // pixels of the launch (its rows x W)
   int row0, row_step;  // traced rows: row0, row0 + row_step, ... (row_step 1: a contiguous band)
   // index arithmetic: when every global sample index of the frame is below
@@ -520,6 +524,14 @@ template <int MODE, bool BVH>
 constexpr bool kInphase() {
   return IPT_INPHASE_REFILL && MODE == MODE_FWDM && !BVH;
 }
+// Small scenes' shading data -- normals, sampling frames, Ke, the emitters'
+// vertices, CDF and pmf -- read from the packed LDS records of scene_layout.h
+// instead of per-lane global loads of TriGeom, TriMat and the emitter arrays
+// (trace_shade_kernel).  0: no launch takes them (A/B timing).
+#ifndef IPT_SHADE_TABLES
+#define IPT_SHADE_TABLES 1
+#endif
+constexpr int kSmallShade = 2;  // TraceArgs::small_pairs bit 1: the launch carries the shading tables
 // Words per pixel of a group's entry table: seed + pixel * spp (lo, hi),
 // (float)c, (float)r -- item_ray_ls's pixel part; a sample adds its index s.
 constexpr int kEntryWords = 4;
@@ -812,6 +824,30 @@ __global__ IPT_TRACE_BOUNDS void trace_kernel(
   constexpr bool MATB = false;
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
+  const int *const tri_emit = nullptr;
+#include "trace_body.h"
+}
+
+// Small scenes (nT <= 32, 0 < nE <= 16): trace_kernel's brute-force forwards
+// and bounded adjoints reading the shading tables of scene_layout.h from LDS
+// (SHADE).  Instances of their own: with both reads in one body
+// behind a wave-uniform branch, the launches that took the old reads ran
+// 1.5-2% slower than before (the branch's SGPRs and code), which is what the
+// tables gain.  trace_kernel's instances stay what they were.
+template <int MODE, bool SPEC, bool BVH>
+__global__ IPT_TRACE_BOUNDS void trace_shade_kernel(
+    const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+    const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat, const float *__restrict__ kd,
+    const int *__restrict__ emit_tri, const float *__restrict__ emit_cdf, const float *__restrict__ emit_pmf,
+    float *__restrict__ out_samples, const float *__restrict__ adj, double *__restrict__ grad,
+    const uint8_t *__restrict__ target, double *__restrict__ edges) {
+  static_assert(!BVH, "the shading tables serve the brute-force instances");
+  constexpr bool MATG = false;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = false;
+  constexpr bool VSETS = false;
+  constexpr bool SHADE = true;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -834,6 +870,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_mat_kernel(
   constexpr bool MATB = true;
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -856,6 +893,7 @@ trace_mat_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const Tr
   constexpr bool MATB = false;
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
 #include "trace_body.h"
 }
 
@@ -878,6 +916,7 @@ trace_matu_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const T
   constexpr bool MATB = false;
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
 #include "trace_body.h"
 }
 
@@ -902,6 +941,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_views_kernel(
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
   constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -920,6 +960,7 @@ trace_mat_views_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, co
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
   constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
 #include "trace_body.h"
 }
 
@@ -943,6 +984,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_views_batch_kernel(
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
   constexpr bool VSETS = true;
+  constexpr bool SHADE = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -962,6 +1004,7 @@ trace_mat_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ ise
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
   constexpr bool VSETS = true;
+  constexpr bool SHADE = false;
 #include "trace_body.h"
 }
 
@@ -989,6 +1032,7 @@ trace_matu_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ is
   constexpr bool MATB = false;
   constexpr bool VIEWS = true;
   constexpr bool VSETS = true;
+  constexpr bool SHADE = false;
 #include "trace_body.h"
 }
 
@@ -1148,8 +1192,10 @@ static std::vector<double> pmf_reciprocals(const std::vector<float> &pmf) {
 // KIND_VBFWD / KIND_VBMAT: the same over (material set, view) pairs
 // (trace_fwd_views_batch_kernel, trace_mat_views_batch_kernel);
 // KIND_VBMAT at MODE_ADJU: the unbounded trace_matu_views_batch_kernel (§21).
-enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4, KIND_VBFWD = 5, KIND_VBMAT = 6 };
-constexpr int kKindLast = KIND_VBMAT;
+// KIND_SHADE: trace_shade_kernel, the small scenes' forwards and bounded adjoints.
+enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4, KIND_VBFWD = 5, KIND_VBMAT = 6, KIND_SHADE = 7 };
+constexpr int kKindLast = KIND_SHADE;
+constexpr bool shade_mode(int mode) { return mode == MODE_FWD || mode == MODE_FWDM || mode == MODE_ADJ || mode == MODE_ADJW; }
 constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }  // ONE material set
 constexpr bool kind_view_sets(int kind) { return kind == KIND_VBFWD || kind == KIND_VBMAT; }
 // The (MODE, KIND) pairs that have kernels (kernel_of's static_asserts).
@@ -1158,6 +1204,7 @@ constexpr bool inst_valid(int mode, int kind) {
          : kind == KIND_MATG ? mode == MODE_ADJ || mode == MODE_ADJU
          : kind == KIND_VMAT ? mode == MODE_ADJ
          : kind == KIND_VBMAT ? mode == MODE_ADJ || mode == MODE_ADJU
+         : kind == KIND_SHADE ? shade_mode(mode)
                              : mode == MODE_FWD || mode == MODE_FWDM;
 }
 // An instance's slot in GpuScene::inst.  0..23: trace_kernel<mode, spec, bvh>;
@@ -1166,7 +1213,8 @@ constexpr bool inst_valid(int mode, int kind) {
 // trace_fwd_views_kernel<FWD | FWDM, spec, bvh>; 48..51: trace_mat_views_kernel<spec, bvh>;
 // 52..59: trace_fwd_views_batch_kernel<FWD | FWDM, spec, bvh>; 60..63:
 // trace_mat_views_batch_kernel<spec, bvh>; 64..67:
-// trace_matu_views_batch_kernel<spec, bvh>.
+// trace_matu_views_batch_kernel<spec, bvh>; 68..91: trace_shade_kernel<mode, spec, false>
+// (one formula for every kind: the BVH slots of KIND_SHADE stay unused).
 constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
   return (kind == KIND_MATG   ? (mode == MODE_ADJU ? 36 : 24)
           : kind == KIND_FWDB ? 28 + (mode == MODE_FWDM ? 4 : 0)
@@ -1174,6 +1222,7 @@ constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
           : kind == KIND_VMAT ? 48
           : kind == KIND_VBFWD ? 52 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VBMAT ? (mode == MODE_ADJU ? 64 : 60)
+          : kind == KIND_SHADE ? 68 + mode * 4
                               : mode * 4) +
          (spec ? 2 : 0) + (bvh ? 1 : 0);
 }
@@ -1451,7 +1500,10 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 // Occupancy queries and the launch itself go through it.
 template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr auto kernel_of() {
-  if constexpr (KIND == KIND_VBMAT) {
+  if constexpr (KIND == KIND_SHADE) {
+    static_assert(shade_mode(MODE), "the shading tables: forwards and bounded adjoints only");
+    return &trace_shade_kernel<MODE, SPEC, BVH>;
+  } else if constexpr (KIND == KIND_VBMAT) {
     static_assert(MODE == MODE_ADJ || MODE == MODE_ADJU, "the view sets' adjoint is the material adjoint, MODE_ADJ or MODE_ADJU");
     if constexpr (MODE == MODE_ADJU) return &trace_matu_views_batch_kernel<SPEC, BVH>;
     else return &trace_mat_views_batch_kernel<SPEC, BVH>;
@@ -1477,7 +1529,8 @@ constexpr auto kernel_of() {
 }
 // ... and its name, for the IPT_DEBUG_GRID prints.
 constexpr const char *kernel_name(int mode, int kind) {
-  return kind == KIND_VBFWD  ? "trace_fwd_views_batch_kernel"
+  return kind == KIND_SHADE  ? "trace_shade_kernel"
+         : kind == KIND_VBFWD ? "trace_fwd_views_batch_kernel"
          : kind == KIND_VBMAT ? (mode == MODE_ADJU ? "trace_matu_views_batch_kernel" : "trace_mat_views_batch_kernel")
          : kind == KIND_VFWD ? "trace_fwd_views_kernel"
          : kind == KIND_VMAT ? "trace_mat_views_kernel"
@@ -1542,7 +1595,7 @@ static TraceArgs make_args(const GpuScene *s, const RenderParams &p) {
   a.nT = s->host.nT;
   a.nE = s->host.nE;
   a.kd_tables = s->host.nT <= kMaxTableTris ? 1 : 0;
-  a.small_pairs = s->host.nT <= 2 * kSmallPairs ? 1 : 0;
+  a.small_pairs = s->host.nT <= 2 * kSmallPairs ? 1 : 0;  // (bit 1: shade_offer, in the entry points that can take the tables)
   a.npix = (uint64_t)rows * p.width;
   a.row0 = p.row_begin;
   a.row_step = p.row_step > 1 ? p.row_step : 1;
@@ -1605,11 +1658,32 @@ static size_t bvh_lds(const GpuScene *s, TraceArgs &a, size_t base, bool stage =
   return head + (size_t)(kBlock / 64) * 8 * a.coop_stride * sizeof(uint32_t) + (lane_words ? kLaneWsBytes : 0);
 }
 
+// The shading tables' bytes at the front of a workgroup's LDS (TraceArgs::small_pairs bit 1)
+static size_t shade_bytes(const TraceArgs &a) {
+  return (a.small_pairs & kSmallShade) ? (size_t)shade_table_words(a.nT, a.nE) * sizeof(uint32_t) : 0;
+}
+// Offered by the entry points whose launch can run a trace_shade_kernel
+// instance (the forwards and the bounded adjoint of a brute-force scene), and
+// by no other: every size and limit an entry point derives from table_bytes
+// then counts the tables exactly where the launch may carry them.
+static void shade_offer(const GpuScene *s, TraceArgs &a) {
+  if (IPT_SHADE_TABLES && (a.small_pairs & 1) && !use_bvh(s) && shade_tables_fit(s->host.nT, s->host.nE))
+    a.small_pairs |= kSmallShade;
+}
+// ... which must not cost a launch a resident workgroup: dropped (bit and
+// bytes) when `lds` + `extra` with them fits fewer workgroups per CU than
+// without, counting up to the `cap` that the instance's registers allow.
+static bool shade_keeps_residency(const TraceArgs &a, size_t lds, size_t extra, size_t cap) {
+  const size_t sh = shade_bytes(a), cu = 160 * 1024;
+  return std::min(cap, cu / (lds + extra)) >= std::min(cap, cu / (lds + extra - sh));
+}
+
 static size_t table_bytes(const TraceArgs &a) {
   return (a.kd_tables ? (size_t)6 * a.nT * sizeof(float) : 0) +
          (a.small_pairs ? (size_t)kE3Floats * ((a.nT + 1) / 2) * sizeof(float) + 12 + (size_t)a.nT * kIsectLdsFloats * sizeof(float) +
                               (IPT_PATH_CULL ? (size_t)((a.nT + 1) / 2) * sizeof(TriPair) : 0) +
-                              (IPT_SHADOW_PO && a.pomask ? (size_t)a.nT * a.nE * sizeof(uint32_t) : 0)
+                              (IPT_SHADOW_PO && a.pomask ? (size_t)a.nT * a.nE * sizeof(uint32_t) : 0) +
+                              shade_bytes(a)
                         : 0);
 }
 
@@ -1901,6 +1975,23 @@ static int launch(GpuScene *s, TraceArgs a, size_t lds, const LaunchIO &io) {
     HIP_TRY(hipGetLastError());
     a.kdpi_g = (const float *)kdpi.p;
   }
+  // The shading tables (shade_offer sets the bit where the scene fits): a
+  // forward or bounded adjoint of a brute-force scene that keeps its resident
+  // workgroups with them runs its trace_shade_kernel instance; every other
+  // launch drops the bit and the bytes.
+  if (a.small_pairs & kSmallShade) {
+    bool take = KIND == KIND_SHADE;
+    if constexpr (KIND == KIND_TRACE && shade_mode(MODE))
+      take = !use_bvh(s) && shade_keeps_residency(a, lds, io.tail ? io.tail + 15 : 0, MODE == MODE_ADJW ? 6 : 5);
+    if (!take) {
+      lds -= shade_bytes(a);
+      a.small_pairs &= ~kSmallShade;
+    }
+    if constexpr (KIND == KIND_TRACE && shade_mode(MODE)) {
+      if (take) return launch<MODE, KIND_SHADE>(s, a, lds, io);
+    }
+    if (KIND == KIND_SHADE && a.n_samples > 0) g_shade_launches.fetch_add(1);
+  }
   auto run = [&](auto spec, auto bvh) {  // the instance: LDS extras of the BVH, then the tail, then the launch
     constexpr bool SPEC = decltype(spec)::value, BVH = decltype(bvh)::value;
     if constexpr (BVH) {
@@ -1915,13 +2006,15 @@ static int launch(GpuScene *s, TraceArgs a, size_t lds, const LaunchIO &io) {
   constexpr std::true_type yes;
   constexpr std::false_type no;
   if constexpr (MODE == MODE_ADJW) return run(no, no);  // (gpu_adjoint: brute-force diffuse scenes only)
+  else if constexpr (KIND == KIND_SHADE) return s->has_ks ? run(yes, no) : run(no, no);
   else if (use_bvh(s)) return s->has_ks ? run(yes, yes) : run(no, yes);
   else return s->has_ks ? run(yes, no) : run(no, no);
 }
 
 int gpu_render_samples(GpuScene *s, const RenderParams &p, const float *kd_dev, float *samples_dev, void *stream) {
   if (check_params(s, p)) return -1;
-  const TraceArgs a = make_args(s, p);
+  TraceArgs a = make_args(s, p);
+  shade_offer(s, a);
   LaunchIO io;
   io.kd = kd_dev, io.out = samples_dev, io.stream = (hipStream_t)stream;
   return launch<MODE_FWD>(s, a, table_bytes(a), io);
@@ -1943,6 +2036,7 @@ static int render_samples_sm(GpuScene *s, const RenderParams &p, const float *kd
   if (check_params(s, p)) return -1;
   TraceArgs a = make_args(s, p);
   a.sample_major = 1;
+  if (KIND == KIND_TRACE) shade_offer(s, a);
   LaunchIO io;
   io.kd = kd_dev, io.out = samples_dev, io.mat = mat_dev, io.views = views_dev, io.nviews = nviews;
   io.stream = (hipStream_t)stream;
@@ -2039,6 +2133,7 @@ static int render_impl(GpuScene *s, const RenderParams &p, const float *kd_dev, 
   const FusedShape fs = fused_shape(p, use_bvh(s));
   if (fs.group > 0) {
     TraceArgs a = make_args(s, p);
+    if (KIND == KIND_TRACE) shade_offer(s, a);
     a.fused = 1;
     a.group = (uint32_t)fs.group;
     a.chunk = (uint32_t)(fs.group * fs.per_grab);  // pixels per grab; launch_inst may halve it for thin launches
@@ -2648,6 +2743,13 @@ int gpu_adjoint(GpuScene *s, const RenderParams &p, const float *kd_dev, const f
   TraceArgs a = adjoint_args(s, p);
   const size_t fields = (size_t)(s->has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
   const size_t per = fields * kBlock * sizeof(float);  // one vertex record (ADJU: ring slot) per lane
+  // (the bounded adjoint may take the shading tables -- unless its records then no longer fit the CU's LDS)
+  if (!unbounded) {
+    shade_offer(s, a);
+    if ((size_t)a.grad_slots * 3 * sizeof(double) + table_bytes(a) + (size_t)kBlock * sizeof(uint32_t) + (size_t)a.rec_cap * per >
+        160 * 1024)
+      a.small_pairs &= ~kSmallShade;
+  }
   const size_t base = (size_t)a.grad_slots * 3 * sizeof(double) + table_bytes(a) +
                       (size_t)kBlock * sizeof(uint32_t);  // + the sweep's owner markers
   if (unbounded) {
@@ -2669,6 +2771,10 @@ int gpu_adjoint(GpuScene *s, const RenderParams &p, const float *kd_dev, const f
   bool wide = !use_bvh(s) && !s->has_ks && 6 * (lds + lane_words) <= 160 * 1024 &&
               (uint64_t)a.n_samples * (uint64_t)std::max(1, a.nscenes) >= IPT_ADJW_MIN_SAMPLES;
   if (const char *e = std::getenv("IPT_ADJW")) wide = std::atoi(e) != 0 && !use_bvh(s) && !s->has_ks;
+  // (a sixth workgroup that only fits without the shading tables: launch<> then drops them)
+  if (!wide && !std::getenv("IPT_ADJW") && !use_bvh(s) && !s->has_ks && 6 * (lds - shade_bytes(a) + lane_words) <= 160 * 1024 &&
+      (uint64_t)a.n_samples * (uint64_t)std::max(1, a.nscenes) >= IPT_ADJW_MIN_SAMPLES)
+    wide = true;
   if (wide) return launch<MODE_ADJW>(s, a, lds + lane_words, io);
   return launch<MODE_ADJ>(s, a, lds, io);
 }

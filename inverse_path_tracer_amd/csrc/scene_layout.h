@@ -87,6 +87,37 @@ struct TriMat {         // 8 floats
 };
 static_assert(sizeof(TriMat) == 32, "TriMat layout");
 
+// ---- small-scene shading tables (trace_body.h)
+// What the shading phase and the emitter term read of TriGeom, TriMat and the
+// emitter arrays, packed once per workgroup into LDS when nT <= 32 and
+// nE <= 16: one record per triangle (plus record nT, the camera's rotation,
+// like TriGeom's) and one per emitter.  The records only move bytes: every
+// word is the bit pattern of the field it copies.
+//
+//   TriShade  word 0-2 vn[0] | 3 TriGeom::flags | TriMat::flags << 8 |
+//             4-12 R | 13-15 Ke
+//   EmitShade word 0 triangle | 1-9 v[0..2] | 10-12 vn[0] | 13 flags (as
+//             above) | 14-16 Ke | 17 emit_pmf | 18-19 emit_pmfr (lo, hi)
+//
+// LDS strides are odd word counts: a TriGeom-like power-of-two stride puts
+// field f of every triangle on one bank, and a wave whose lanes hold ten
+// different triangles would read it in ten passes.  With an odd stride the
+// <= 33 (<= 16) records' field f sit on distinct banks of the 64.
+constexpr int kTriShadeWords = 16, kTriShadeStride = 17;
+constexpr int kEmitShadeWords = 20, kEmitShadeStride = 21;
+constexpr int kShadeMaxTris = 32, kShadeMaxEmit = 16;
+enum : int { TS_VN = 0, TS_FLAGS = 3, TS_R = 4, TS_KE = 13 };
+enum : int { ES_TRI = 0, ES_V = 1, ES_VN = 10, ES_FLAGS = 13, ES_KE = 14, ES_PMF = 17, ES_PMFR = 18 };
+// the emitters' CDF in front of the records, padded with NaN (never >= u) to
+// kShadeMaxEmit words so that the walk reads 16 B at a time
+constexpr int kShadeCdfWords = kShadeMaxEmit;
+constexpr bool shade_tables_fit(int nT, int nE) { return nT <= kShadeMaxTris && nE > 0 && nE <= kShadeMaxEmit; }
+// LDS words of the tables (the CDF first), a multiple of four: 16-B aligned
+// at the front of the workgroup's LDS, they leave what follows aligned as it was
+constexpr int shade_table_words(int nT, int nE) {
+  return (kShadeCdfWords + (nT + 1) * kTriShadeStride + nE * kEmitShadeStride + 3) & ~3;
+}
+
 // ---- triangle BVH (bvh.cpp) for scenes past the brute-force size
 // The reference's BVH (bvh.h:109-205) is over OBJECTS and, for the shipped
 // scenes (<= 4 objects), a single leaf: its closest hit is brute force over

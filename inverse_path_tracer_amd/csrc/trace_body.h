@@ -13,7 +13,8 @@
 // cameras over one material set, DESIGN.md §18: the view kernels' trailing
 // parameter is the views' table, read by its kernarg offset), and VSETS (with
 // VIEWS: the sets are (material set, view) pairs, DESIGN.md §20 -- the view
-// count V follows the table as one more trailing parameter).
+// count V follows the table as one more trailing parameter), and SHADE (the
+// small scenes' shading tables in LDS, DESIGN.md §23: trace_shade_kernel).
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   // scene batch: this workgroup's material set and its place among the set's blocks
@@ -48,8 +49,22 @@
   constexpr int nthr = kBlock;
   const int nT = a.nT, nE = a.nE;
   const int vmax = a.rec_cap;  // ADJ record capacity per lane (ADJU: ring slots)
-  // LDS: [fp64 accumulators][kd table][kd/pi table][ADJ vertex records]
+  // SHADE (trace_shade_kernel; small scenes with <= kShadeMaxEmit emitters):
+  // the shading tables (scene_layout.h) -- the emitters' CDF, a
+  // TriShade record per triangle and for the camera, an EmitShade record per
+  // emitter -- at the front of the workgroup's LDS, so that their addresses
+  // are constants plus the record's offset and no base is held through the
+  // trace loop.  The host launches a SHADE instance exactly when it has set
+  // TraceArgs::small_pairs bit 1 and added the bytes (launch<>, table_bytes).
+  // the emitter's triangle: taken with its vertices and held to the shadow
+  // cast, or (the six-wave adjoint and the Phong per-sample forward, which it
+  // would push to 16 B of scratch per lane) read again from the record in
+  // front of the cast
+  constexpr bool kEtEarly = !(MODE == MODE_ADJW || (MODE == MODE_FWD && SPEC));
+  float *lds_sh = reinterpret_cast<float *>(lds);
+  // LDS: [shading tables][fp64 accumulators][kd table][kd/pi table][ADJ vertex records]
   double *lds_acc = lds;               // ADJ: nT*3 grad; GRAPH: (nT+1)*nT*kEdgeW bins
+  if (SHADE) lds_acc += shade_table_words(nT, nE) / 2;
   int n_acc = 0;
   if (is_adj<MODE>()) {
     n_acc = a.grad_slots * 3;
@@ -62,7 +77,7 @@
   // M_PI`, path_trace.cu:15-17): computed once per workgroup with the same
   // IEEE division the per-vertex code would do, instead of three divisions
   // per vertex.  Falls back to global memory for large scenes.
-  float *tab = reinterpret_cast<float *>(lds + n_acc);
+  float *tab = reinterpret_cast<float *>((SHADE ? lds_acc : lds) + n_acc);
   if (a.kd_tables) {
     for (int i = tid; i < 3 * nT; i += nthr) {
       const float v = kd[i];
@@ -78,10 +93,6 @@
   auto kd3 = [&](int t) -> V3 {
     if (a.kd_tables) return mk(tab_l[3 * t], tab_l[3 * t + 1], tab_l[3 * t + 2]);
     return mk(kd_g[3 * t], kd_g[3 * t + 1], kd_g[3 * t + 2]);
-  };
-  auto ke3 = [&](int t) -> V3 {  // TriMat::ke
-    const gbl_f32 *q = (const gbl_f32 *)mat + (size_t)t * (sizeof(TriMat) / sizeof(float)) + offsetof(TriMat, ke) / sizeof(float);
-    return mk(q[0], q[1], q[2]);
   };
   auto kdpi3 = [&](int t) -> V3 {
     if (a.kd_tables) return mk(tab_l[3 * nT + 3 * t], tab_l[3 * nT + 3 * t + 1], tab_l[3 * nT + 3 * t + 2]);
@@ -117,7 +128,34 @@
   const bool po = a.small_pairs && IPT_SHADOW_PO && a.pomask;
   if (po)
     for (int i = tid; i < nT * nE; i += nthr) lds_po[i] = a.pomask[i];
+  if (SHADE) {  // the shading tables' fill
+    uint32_t *w = reinterpret_cast<uint32_t *>(lds_sh);
+    const uint32_t *gw = reinterpret_cast<const uint32_t *>(geom), *mw = reinterpret_cast<const uint32_t *>(mat);
+    constexpr int GW = sizeof(TriGeom) / 4, MW = sizeof(TriMat) / 4;
+    for (int i = tid; i < kShadeCdfWords; i += nthr) w[i] = i < nE ? __float_as_uint(emit_cdf[i]) : 0x7fc00000u;
+    w += kShadeCdfWords;
+    for (int i = tid; i < (nT + 1) * kTriShadeWords; i += nthr) {
+      const int t = i / kTriShadeWords, f = i % kTriShadeWords;
+      w[t * kTriShadeStride + f] = tri_shade_word(gw + (size_t)t * GW, t < nT ? mw + (size_t)t * MW : nullptr, f);
+    }
+    w += (nT + 1) * kTriShadeStride;
+    for (int i = tid; i < nE * kEmitShadeWords; i += nthr) {
+      const int e = i / kEmitShadeWords, f = i % kEmitShadeWords, t = emit_tri[e];
+      w[e * kEmitShadeStride + f] = emit_shade_word(gw + (size_t)t * GW, mw + (size_t)t * MW, t, emit_pmf[e], a.emit_pmfr[e], f);
+    }
+  }
+  const lds_f32 *cdf_l = (const lds_f32 *)lds_sh;
+  const lds_f32 *tsh = cdf_l + kShadeCdfWords;                    // TriShade of triangle t at tsh + t * kTriShadeStride
+  const lds_f32 *esh = tsh + (nT + 1) * kTriShadeStride;          // EmitShade of emitter e at esh + e * kEmitShadeStride
   float *lds_rec = a.small_pairs ? reinterpret_cast<float *>(lds_po) + (po ? nT * nE : 0) : lds_e3;
+  auto ke3 = [&](int t) -> V3 {  // TriMat::ke
+    if (SHADE) {
+      const lds_f32 *r = tsh + t * kTriShadeStride + TS_KE;
+      return mk(r[0], r[1], r[2]);
+    }
+    const gbl_f32 *q = (const gbl_f32 *)mat + (size_t)t * (sizeof(TriMat) / sizeof(float)) + offsetof(TriMat, ke) / sizeof(float);
+    return mk(q[0], q[1], q[2]);
+  };
   // the unbounded material adjoint, brute force (96 VGPRs): the owner lane's
   // carried state -- Scar, Mlo, the path's first triangle and the work item,
   // each touched once per chunk -- in kCarryWords LDS words per lane instead of registers
@@ -680,7 +718,7 @@
     // and it has taken its next sample, the item nitem (slot | s << 4)
     bool wantc = false, refill = false;
     uint32_t nitem = 0;
-    int emitter = 0;
+    int emitter = 0, et_sh = 0;
     float ct = 0.f, coeff = 0.f, speci = 0.f, specd = 0.f;
     if (vertex) {
       const V3 q = along(p, d, t);
@@ -698,23 +736,65 @@
           else tri0_r = tri;
         }
       }
-      nh = shading_normal(geom[tri], q);
+      if (SHADE) {  // the flat normal from the triangle's record; a wave without other triangles pays nothing more
+        const lds_f32 *r = tsh + tri * kTriShadeStride;
+        const bool flat = (__float_as_uint(r[TS_FLAGS]) & GEOM_AXIS_FLAT) != 0u;
+        nh = mk(r[TS_VN], r[TS_VN + 1], r[TS_VN + 2]);
+        if (__ballot(!flat)) {
+          if (!flat) nh = shading_normal(geom[tri], q);
+        }
+      } else {
+        nh = shading_normal(geom[tri], q);
+      }
       p = q;
       Ld = mk(0.f, 0.f, 0.f);
       if (nE > 0) {  // directLighting up to the shadow ray, path_trace.cu:30-71
         const float u = uniform(st);
         int ie = 0;
-        while (ie < nE && !(emit_cdf[ie] >= u)) ++ie;
-        ie = ie < nE ? ie : nE - 1;
+        if (SHADE) {
+          // the CDF is the same for every lane: a wave-uniform walk over its LDS
+          // copy, 16 B per read (broadcast), the first i with cdf[i] >= u kept
+          // per lane -- the loop below without its per-lane loads (the NaN
+          // padding behind entry nE-1 is never >= u; no monotone CDF assumed)
+          ie = nE - 1;
+          bool found = false;
+          for (int i = 0; i < nE; i += 4) {
+            const v4f c = *(const lds_v4 *)(cdf_l + i);
+            const bool h0 = !found && c.x >= u;
+            ie = h0 ? i : ie;
+            found = found || h0;
+            const bool h1 = !found && c.y >= u;
+            ie = h1 ? i + 1 : ie;
+            found = found || h1;
+            const bool h2 = !found && c.z >= u;
+            ie = h2 ? i + 2 : ie;
+            found = found || h2;
+            const bool h3 = !found && c.w >= u;
+            ie = h3 ? i + 3 : ie;
+            found = found || h3;
+          }
+        } else {
+          while (ie < nE && !(emit_cdf[ie] >= u)) ++ie;
+          ie = ie < nE ? ie : nE - 1;
+        }
         const float r1 = uniform(st), r2 = uniform(st);
         const double sq = dsqrt_core((double)r1);  // r1 >= 2^-33: sqrt's identity range
         const float ca = (float)(1.0 - sq);
         const float cb = (float)(sq * (double)(1.f - r2));
         const float cc = (float)((double)r2 * sq);
-        const TriGeom &ge = geom[emit_tri[ie]];
-        const V3 pt = mk(fmaf(cc, ge.v[2][0], fmaf(cb, ge.v[1][0], ca * ge.v[0][0])),
-                         fmaf(cc, ge.v[2][1], fmaf(cb, ge.v[1][1], ca * ge.v[0][1])),
-                         fmaf(cc, ge.v[2][2], fmaf(cb, ge.v[1][2], ca * ge.v[0][2])));
+        V3 pt;
+        if (SHADE) {  // the emitter's vertices (and its triangle) from its record
+          const lds_f32 *er = esh + ie * kEmitShadeStride;
+          if (kEtEarly) et_sh = (int)__float_as_uint(er[ES_TRI]);
+          const lds_f32 *ev = er + ES_V;
+          pt = mk(fmaf(cc, ev[6], fmaf(cb, ev[3], ca * ev[0])), fmaf(cc, ev[7], fmaf(cb, ev[4], ca * ev[1])),
+                  fmaf(cc, ev[8], fmaf(cb, ev[5], ca * ev[2])));
+        } else {
+          const TriGeom &ge = geom[emit_tri[ie]];
+          pt = mk(fmaf(cc, ge.v[2][0], fmaf(cb, ge.v[1][0], ca * ge.v[0][0])),
+                  fmaf(cc, ge.v[2][1], fmaf(cb, ge.v[1][1], ca * ge.v[0][1])),
+                  fmaf(cc, ge.v[2][2], fmaf(cb, ge.v[1][2], ca * ge.v[0][2])));
+        }
         sd = unit(sub(pt, q));
         ct = dot3(nh, sd);
         emitter = ie;
@@ -726,7 +806,9 @@
           wantc = pr < kPRR;
         } else if (pr < kPRR) {         // sampleNextDir, path_trace.cu:91-109
           const TriMat &m = mat[tri];
-          const bool spec = SPEC && (MODE != MODE_GRAPH) && (m.flags & MAT_SPECULAR);
+          // (SHADE: TriMat::flags from the record's flags word)
+          const uint32_t sflags = SPEC && SHADE ? __float_as_uint(tsh[tri * kTriShadeStride + TS_FLAGS]) >> 8 : 0u;
+          const bool spec = SPEC && (MODE != MODE_GRAPH) && ((SHADE ? sflags : m.flags) & MAT_SPECULAR);
           const float uphi = uniform(st);
           const float phi = (float)(2.0 * kPi * (double)uphi);
           const float ut = uniform(st);
@@ -747,12 +829,18 @@
           float sp, cp;
           sincos_f(phi, sp, cp);
           const V3 h = mk(sth * cp, sth * sp, cth);
-          const TriGeom &g = geom[tri];
-          nd = unit(mk(fmaf(g.R[0][2], h.z, fmaf(g.R[0][1], h.y, g.R[0][0] * h.x)),
-                       fmaf(g.R[1][2], h.z, fmaf(g.R[1][1], h.y, g.R[1][0] * h.x)),
-                       fmaf(g.R[2][2], h.z, fmaf(g.R[2][1], h.y, g.R[2][0] * h.x))));
+          if (SHADE) {
+            const lds_f32 *R = tsh + tri * kTriShadeStride + TS_R;
+            nd = unit(mk(fmaf(R[2], h.z, fmaf(R[1], h.y, R[0] * h.x)), fmaf(R[5], h.z, fmaf(R[4], h.y, R[3] * h.x)),
+                         fmaf(R[8], h.z, fmaf(R[7], h.y, R[6] * h.x))));
+          } else {
+            const TriGeom &g = geom[tri];
+            nd = unit(mk(fmaf(g.R[0][2], h.z, fmaf(g.R[0][1], h.y, g.R[0][0] * h.x)),
+                         fmaf(g.R[1][2], h.z, fmaf(g.R[1][1], h.y, g.R[1][0] * h.x)),
+                         fmaf(g.R[2][2], h.z, fmaf(g.R[2][1], h.y, g.R[2][0] * h.x))));
+          }
           if (MODE != MODE_GRAPH) {
-            if (SPEC && (m.flags & MAT_HAS_KS)) speci = phong(m.shininess, nh, din, nd);
+            if (SPEC && ((SHADE ? sflags : m.flags) & MAT_HAS_KS)) speci = phong(m.shininess, nh, din, nd);
             coeff = spec ? (dot3(nd, nh) / psamp) / kPRR : div_const<1>(div_const<0>(dot3(nd, nh)));  // psamp = kInvPiF
           }
           cont = true;
@@ -794,7 +882,9 @@
         const float ua = uniform(st);  // cont: phi's draw; refill: the camera's u0
         const float ub = uniform(st);  // cont: theta's;    refill: u1
         const TriMat &m = mat[refill ? 0 : tri];
-        const bool spec = SPEC && !refill && (m.flags & MAT_SPECULAR);
+        // (SHADE: TriMat::flags from the record's flags word)
+        const uint32_t sflags = SPEC && SHADE ? __float_as_uint(tsh[(refill ? 0 : tri) * kTriShadeStride + TS_FLAGS]) >> 8 : 0u;
+        const bool spec = SPEC && !refill && ((SHADE ? sflags : m.flags) & MAT_SPECULAR);
         float psamp = kInvPiF;
         V3 h;
         if (refill) {
@@ -816,12 +906,19 @@
           sincos_f(phi, sp, cp);
           h = mk(sth * cp, sth * sp, cth);
         }
-        const TriGeom &g = geom[refill ? nT : tri];
-        V3 v = rotate3(g.R[0], g.R[1], g.R[2], h);
+        V3 v;
+        if (SHADE) {  // (the camera's rotation is record nT of the table, as of geom)
+          const lds_f32 *R = tsh + (refill ? nT : tri) * kTriShadeStride + TS_R;
+          v = mk(fmaf(R[2], h.z, fmaf(R[1], h.y, R[0] * h.x)), fmaf(R[5], h.z, fmaf(R[4], h.y, R[3] * h.x)),
+                 fmaf(R[8], h.z, fmaf(R[7], h.y, R[6] * h.x)));  // rotate3's chain
+        } else {
+          const TriGeom &g = geom[refill ? nT : tri];
+          v = rotate3(g.R[0], g.R[1], g.R[2], h);
+        }
         if (refill) v = camera_w0(a.cam, v);  // Ray::transform's w term: these lanes only
         nd = unit(v);
         if (wantc) {
-          if (SPEC && (m.flags & MAT_HAS_KS)) speci = phong(m.shininess, nh, din, nd);
+          if (SPEC && ((SHADE ? sflags : m.flags) & MAT_HAS_KS)) speci = phong(m.shininess, nh, din, nd);
           coeff = spec ? (dot3(nd, nh) / psamp) / kPRR : div_const<1>(div_const<0>(dot3(nd, nh)));  // psamp = kInvPiF
           cont = true;
         }
@@ -836,7 +933,10 @@
     int emit_et = 0;
     float ts = 0.f;
     int hs = -1;
-    const int et = shadow ? emit_tri[emitter] : -1;
+    const int et = !shadow ? -1
+                   : !SHADE   ? emit_tri[emitter]
+                   : kEtEarly ? et_sh
+                              : (int)__float_as_uint(esh[emitter * kEmitShadeStride + ES_TRI]);
     if (__ballot(shadow)) {
       PHASE_LANES(14, shadow)
       if (BVH) {
@@ -856,18 +956,40 @@
       }
       PHASE(3)
       if (shadow && hs == et) {  // must hit the sampled emitter itself
-        const V3 ne = shading_normal(geom[et], along(p, sd, ts));
+        // SHADE: the emitter's record -- normal and flags, then, on the lanes that
+        // face it, Ke, pmf and its reciprocal (asked for with the normal they
+        // cost the fused forward three registers it does not have)
+        V3 ne;
+        if (SHADE) {
+          const lds_f32 *er = esh + emitter * kEmitShadeStride;
+          const bool flat = (__float_as_uint(er[ES_FLAGS]) & GEOM_AXIS_FLAT) != 0u;
+          ne = mk(er[ES_VN], er[ES_VN + 1], er[ES_VN + 2]);
+          if (__ballot(!flat)) {
+            if (!flat) ne = shading_normal(geom[et], along(p, sd, ts));
+          }
+        } else {
+          ne = shading_normal(geom[et], along(p, sd, ts));
+        }
         const float ctp = -dot3(ne, sd);
         if (!(ctp < 0.f)) {
           const double td = (double)ts;
-          const TriMat &me = mat[et];
+          V3 kee_s = mk(0.f, 0.f, 0.f);
+          double pr_s = 0.0;
+          float pmf_s = 0.f;
+          if (SHADE) {
+            const lds_f32 *er = esh + emitter * kEmitShadeStride;
+            kee_s = mk(er[ES_KE], er[ES_KE + 1], er[ES_KE + 2]);
+            pmf_s = er[ES_PMF];
+            pr_s = __hiloint2double((int)__float_as_uint(er[ES_PMFR + 1]), (int)__float_as_uint(er[ES_PMFR]));
+          }
           if (MODE == MODE_GRAPH) {
-            const double q = (double)((weight * ct) * ctp) / (td * td), pr = a.emit_pmfr[emitter];
+            const TriMat &me = mat[et];
+            const double q = (double)((weight * ct) * ctp) / (td * td), pr = SHADE ? pr_s : a.emit_pmfr[emitter];
             double w2d;
             if (pr != 0.0)
               w2d = q * pr;
             else
-              w2d = q / (double)emit_pmf[emitter];
+              w2d = q / (double)(SHADE ? pmf_s : emit_pmf[emitter]);
             const float w2 = (float)w2d;
             const float wf = w2 * kInvPiF;  // BSDF(direct) factor 1/pi, inv_path_trace.cu:8
             const double v[8] = {(double)w2, (double)wf, (double)(wf * pix.x), (double)(wf * pix.y),
@@ -881,14 +1003,14 @@
               bins_add(false, edges, bin * kEdgeW, 8, v);
             }
           } else {
-            const double q = (double)(ct * ctp) / (td * td), pr = a.emit_pmfr[emitter];
+            const double q = (double)(ct * ctp) / (td * td), pr = SHADE ? pr_s : a.emit_pmfr[emitter];
             double s64;
             if (pr != 0.0)
               s64 = q * pr;
             else
-              s64 = q / (double)emit_pmf[emitter];
+              s64 = q / (double)(SHADE ? pmf_s : emit_pmf[emitter]);
             const float s = (float)s64;
-            const V3 kee = ke3(et);
+            const V3 kee = SHADE ? kee_s : ke3(et);
             lo = mk(kee.x * s, kee.y * s, kee.z * s);
             emit_s = s;
             emit_et = et;
