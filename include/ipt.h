@@ -246,6 +246,30 @@ int ipt_render_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, 
 int ipt_adjoint_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
                         const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream);
 int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj /*H*W*3*/, double *grad /*3*nT*3*/);
+/* Forward mode of the same estimator: n_tangents directions in material space
+ * -> n_tangents tangent images in ONE launch (the paths are traced once).
+ * tkd_dev / tks_dev / tke_dev: n_tangents*nT*3 floats [k][tri][c], each
+ * nullable as a whole (NULL = all zero; at least one must be given); Ks rows
+ * of lobe-less triangles and Ke rows of non-emitters are never read (the
+ * frozen structure).  tan_dev: n_tangents*rows*W*3 doubles [k][row][col][c]
+ * over the rows of p's band in band order, like hdr, ACCUMULATED (zero it
+ * first).  tan[k][p][c] = <ipt_adjoint_mat_dev's gradient under the one-hot
+ * adjoint image at pixel p, tangent k> in channel c, up to fp64 summation
+ * order: every fp32 term a*g of the adjoint's sweep (a = 1/spp), widened to
+ * double, times the tangent's entry of the bin it would have gone to.  It is
+ * the derivative of ipt_render_mat_dev's HDR mean along tangent k under the
+ * forward's own paths.  One material set, the scene's own camera.  Refused
+ * with an error before anything is enqueued: n_tangents outside 1..16, all
+ * three tangent pointers NULL, max_bounces < 0 or > 62, more than 65535
+ * triangles, a host-only scene, an LDS footprint (tangent tables of scenes up
+ * to 512 triangles: n_tangents*(2*nT + nE)*12 bytes at most, plus tables and
+ * vertex records) over 160 KiB.  The host form takes the scene's own material
+ * values.  (Additive symbols: ipt_abi_version stays 5.) */
+int ipt_tangent_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                        const float *ke_dev, int n_tangents, const float *tkd_dev, const float *tks_dev,
+                        const float *tke_dev, double *tan_dev, void *stream);
+int ipt_tangent_mat_host(void *scene, const ipt_params_t *p, int n_tangents, const float *tkd /*K*nT*3*/,
+                         const float *tks, const float *tke, double *tan /*K*rows*W*3*/);
 /* The same for the reference's own estimator (max_bounces = -1: no bounce cap,
  * Russian roulette at 0.9), whose forward is ipt_render_mat_dev with
  * max_bounces = -1: one launch of the unbounded adjoint's ring-and-replay

@@ -110,6 +110,8 @@ SIGNATURES = {
     "ipt_render_mat_dev": (C.c_int, [vp, pp, vp, vp, vp, vp, vp, vp]),
     "ipt_adjoint_mat_dev": (C.c_int, [vp, pp, vp, vp, vp, vp, vp, vp]),
     "ipt_adjoint_mat_host": (C.c_int, [vp, pp, fp, dp]),
+    "ipt_tangent_mat_dev": (C.c_int, [vp, pp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
+    "ipt_tangent_mat_host": (C.c_int, [vp, pp, C.c_int, fp, fp, fp, dp]),
     "ipt_adjoint_mat_unbounded_dev": (C.c_int, [vp, pp, vp, vp, vp, vp, vp, vp]),
     "ipt_adjoint_mat_unbounded_host": (C.c_int, [vp, pp, fp, dp]),
     "ipt_render_mat_batch_dev": (C.c_int, [vp, pp, C.c_int, C.c_uint64, vp, vp, vp, vp, vp]),

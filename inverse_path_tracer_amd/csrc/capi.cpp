@@ -484,6 +484,28 @@ int ipt_adjoint_mat_host(void *scene, const ipt_params_t *p, const float *adj, d
   return gpu_status(ipt::gpu_adjoint_mat_host(s, to_params(p), adj, grad));
 }
 
+int ipt_tangent_mat_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
+                        const float *ke_dev, int n_tangents, const float *tkd_dev, const float *tks_dev,
+                        const float *tke_dev, double *tan_dev, void *stream) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !tan_dev) {
+    if (s) fail("ipt_tangent_mat_dev: bad arguments (params and tan_dev are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_tangent_mat(s, to_params(p), kd_dev, ks_dev, ke_dev, n_tangents, tkd_dev, tks_dev, tke_dev,
+                                         tan_dev, stream));
+}
+
+int ipt_tangent_mat_host(void *scene, const ipt_params_t *p, int n_tangents, const float *tkd, const float *tks,
+                         const float *tke, double *tan) {
+  GpuScene *s = as_scene(scene);
+  if (!s || !p || !tan) {
+    if (s) fail("ipt_tangent_mat_host: bad arguments (params and tan are required)");
+    return -1;
+  }
+  return gpu_status(ipt::gpu_tangent_mat_host(s, to_params(p), n_tangents, tkd, tks, tke, tan));
+}
+
 int ipt_adjoint_mat_unbounded_dev(void *scene, const ipt_params_t *p, const float *kd_dev, const float *ks_dev,
                                   const float *ke_dev, const float *adj_dev, double *grad_dev, void *stream) {
   GpuScene *s = as_scene(scene);

@@ -51,6 +51,16 @@ int gpu_render_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, cons
 int gpu_adjoint_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
                     const float *adj_dev, double *grad_dev, void *stream);
 int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad);
+// Forward mode of the same estimator: n_tangents directions in material space (tkd / tks / tke, each
+// n_tangents x nT x 3 floats, nullptr = zero, at least one given; 1 <= n_tangents <= 16) -> tan_dev,
+// n_tangents x band rows x W x 3 doubles, accumulated: tangent image k is the derivative of the HDR mean
+// along direction k under the forward's own paths.  One launch of trace_tan_kernel; refuses what
+// gpu_adjoint_mat refuses.  The host form takes the scene's own values.
+int gpu_tangent_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
+                    int n_tangents, const float *tkd_dev, const float *tks_dev, const float *tke_dev, double *tan_dev,
+                    void *stream);
+int gpu_tangent_mat_host(GpuScene *s, const RenderParams &p, int n_tangents, const float *tkd, const float *tks,
+                         const float *tke, double *tan);
 // The same three blocks for the unbounded estimator (max_bounces < 0; one launch of
 // trace_matu_kernel).  Refuses max_bounces >= 0 and the scene batch.
 int gpu_adjoint_mat_unbounded(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev,

@@ -126,6 +126,14 @@ __host__ __device__ inline size_t graph_lds_doubles(int nT, int nE) {
 __host__ __device__ inline size_t mat_lds_doubles(int grad_slots, int nE, bool spec) {
   return (size_t)grad_slots * 3 * (spec ? 2 : 1) + (size_t)(nE > 0 ? nE : 0) * 3;
 }
+// LDS tangent tables of the tangent launch (trace_tan_kernel), in doubles (the
+// accumulators' place: it has no bins): for scenes with kd tables, ntan x
+// (nT x 3 Kd, as many Ks with the Phong lobe, nE x 3 Ke by emitter) floats,
+// rounded up to whole doubles; larger scenes read the tangents from global memory.
+constexpr int kMaxTangents = 16;
+__host__ __device__ inline size_t tan_lds_doubles(int ntan, int nT, int nE, bool spec, bool tables) {
+  return tables ? ((size_t)ntan * 3 * ((size_t)nT * (spec ? 2 : 1) + (size_t)(nE > 0 ? nE : 0)) + 1) / 2 : 0;
+}
 // The unbounded material adjoint's brute-force instances keep the owner
 // lane's carried state (Scar, Mlo, the first triangle, the work item) in LDS:
 // words per lane, in front of the owner markers (trace_body.h, kCarryLds).
@@ -825,6 +833,7 @@ __global__ IPT_TRACE_BOUNDS void trace_kernel(
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -848,6 +857,7 @@ __global__ IPT_TRACE_BOUNDS void trace_shade_kernel(
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
   constexpr bool SHADE = true;
+  constexpr bool TANG = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -871,6 +881,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_mat_kernel(
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -894,6 +905,7 @@ trace_mat_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const Tr
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
 #include "trace_body.h"
 }
 
@@ -917,6 +929,7 @@ trace_matu_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const T
   constexpr bool VIEWS = false;
   constexpr bool VSETS = false;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
 #include "trace_body.h"
 }
 
@@ -942,6 +955,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_views_kernel(
   constexpr bool VIEWS = true;
   constexpr bool VSETS = false;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -961,6 +975,7 @@ trace_mat_views_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, co
   constexpr bool VIEWS = true;
   constexpr bool VSETS = false;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
 #include "trace_body.h"
 }
 
@@ -985,6 +1000,7 @@ __global__ IPT_TRACE_BOUNDS void trace_fwd_views_batch_kernel(
   constexpr bool VIEWS = true;
   constexpr bool VSETS = true;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
   const int *const tri_emit = nullptr;
 #include "trace_body.h"
 }
@@ -1005,6 +1021,7 @@ trace_mat_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ ise
   constexpr bool VIEWS = true;
   constexpr bool VSETS = true;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
 #include "trace_body.h"
 }
 
@@ -1033,6 +1050,35 @@ trace_matu_views_batch_kernel(const TraceArgs a, const TriIsect *__restrict__ is
   constexpr bool VIEWS = true;
   constexpr bool VSETS = true;
   constexpr bool SHADE = false;
+  constexpr bool TANG = false;
+#include "trace_body.h"
+}
+
+// Forward-mode material derivatives: trace_mat_kernel's
+// tracing, records, chains and fp32 terms; the sweep's last step multiplies
+// each term by the tangents' entry for the bin the adjoint would have added it
+// to and sums per pixel.  No adjoint image (the weights are 1/spp) and no bins:
+// `grad` is the tangent images, ntan x npix x 3 doubles, accumulated.  The
+// tangents (ntan x nT x 3 floats each, nullptr: zero) follow tri_emit, read by
+// their kernarg offsets (TanKernArgs).  A __global__ of its own, named so that
+// no count of the other families by prefix sees it.
+template <bool SPEC, bool BVH>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
+                          amdgpu_waves_per_eu(min_blocks<MODE_ADJ, BVH>()))) void
+trace_tan_kernel(const TraceArgs a, const TriIsect *__restrict__ isect, const TriPair *__restrict__ pairs,
+                 const TriGeom *__restrict__ geom, const TriMat *__restrict__ mat, const float *__restrict__ kd,
+                 const int *__restrict__ emit_tri, const float *__restrict__ emit_cdf,
+                 const float *__restrict__ emit_pmf, float *__restrict__ out_samples, const float *__restrict__ adj,
+                 double *__restrict__ grad, const uint8_t *__restrict__ target, double *__restrict__ edges,
+                 const int *__restrict__ tri_emit, const float *__restrict__ tkd_arg, const float *__restrict__ tks_arg,
+                 const float *__restrict__ tke_arg, const int ntan_arg) {
+  constexpr int MODE = MODE_ADJ;
+  constexpr bool MATG = true;
+  constexpr bool MATB = false;
+  constexpr bool VIEWS = false;
+  constexpr bool VSETS = false;
+  constexpr bool SHADE = false;
+  constexpr bool TANG = true;
 #include "trace_body.h"
 }
 
@@ -1193,8 +1239,9 @@ static std::vector<double> pmf_reciprocals(const std::vector<float> &pmf) {
 // (trace_fwd_views_batch_kernel, trace_mat_views_batch_kernel);
 // KIND_VBMAT at MODE_ADJU: the unbounded trace_matu_views_batch_kernel (§21).
 // KIND_SHADE: trace_shade_kernel, the small scenes' forwards and bounded adjoints.
-enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4, KIND_VBFWD = 5, KIND_VBMAT = 6, KIND_SHADE = 7 };
-constexpr int kKindLast = KIND_SHADE;
+// KIND_TANG: trace_tan_kernel, the bounded material adjoint's tangent launch.
+enum { KIND_TRACE = 0, KIND_MATG = 1, KIND_FWDB = 2, KIND_VFWD = 3, KIND_VMAT = 4, KIND_VBFWD = 5, KIND_VBMAT = 6, KIND_SHADE = 7, KIND_TANG = 8 };
+constexpr int kKindLast = KIND_TANG;
 constexpr bool shade_mode(int mode) { return mode == MODE_FWD || mode == MODE_FWDM || mode == MODE_ADJ || mode == MODE_ADJW; }
 constexpr bool kind_views(int kind) { return kind == KIND_VFWD || kind == KIND_VMAT; }  // ONE material set
 constexpr bool kind_view_sets(int kind) { return kind == KIND_VBFWD || kind == KIND_VBMAT; }
@@ -1205,6 +1252,7 @@ constexpr bool inst_valid(int mode, int kind) {
          : kind == KIND_VMAT ? mode == MODE_ADJ
          : kind == KIND_VBMAT ? mode == MODE_ADJ || mode == MODE_ADJU
          : kind == KIND_SHADE ? shade_mode(mode)
+         : kind == KIND_TANG ? mode == MODE_ADJ
                              : mode == MODE_FWD || mode == MODE_FWDM;
 }
 // An instance's slot in GpuScene::inst.  0..23: trace_kernel<mode, spec, bvh>;
@@ -1214,9 +1262,12 @@ constexpr bool inst_valid(int mode, int kind) {
 // 52..59: trace_fwd_views_batch_kernel<FWD | FWDM, spec, bvh>; 60..63:
 // trace_mat_views_batch_kernel<spec, bvh>; 64..67:
 // trace_matu_views_batch_kernel<spec, bvh>; 68..91: trace_shade_kernel<mode, spec, false>
-// (one formula for every kind: the BVH slots of KIND_SHADE stay unused).
+// (one formula for every kind: the BVH slots of KIND_SHADE stay unused);
+// 92..95: trace_tan_kernel<spec, bvh>.
 constexpr int inst_slot(int mode, bool spec, bool bvh, int kind) {
+  static_assert(MODE_ADJW == 5, "KIND_SHADE's slots end at 91");
   return (kind == KIND_MATG   ? (mode == MODE_ADJU ? 36 : 24)
+          : kind == KIND_TANG ? 92
           : kind == KIND_FWDB ? 28 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VFWD ? 40 + (mode == MODE_FWDM ? 4 : 0)
           : kind == KIND_VMAT ? 48
@@ -1468,11 +1519,17 @@ int gpu_device_count() {
   return n;
 }
 
-static int check_params(const GpuScene *s, const RenderParams &p) {
+static int check_frame(const GpuScene *s, const RenderParams &p);
+static int check_device(const GpuScene *s) {
   if (!s->on_device) {
     gpu_set_error("scene was loaded host-only (ipt_load_scene_host); it cannot be rendered");
     return -1;
   }
+  return 0;
+}
+static int check_params(const GpuScene *s, const RenderParams &p) { return check_device(s) || check_frame(s, p) ? -1 : 0; }
+// (the frame alone: an entry point that refuses on its own arguments before it asks for a device)
+static int check_frame(const GpuScene *s, const RenderParams &p) {
   if (p.width <= 0 || p.height <= 0 || p.spp <= 0 || p.row_begin < 0 || p.row_end > p.height ||
       p.row_begin > p.row_end || p.row_step < 1) {
     gpu_set_error("invalid render parameters (width/height/spp > 0, 0 <= row_begin <= row_end <= height, row_step >= 1)");
@@ -1500,7 +1557,10 @@ static int check_params(const GpuScene *s, const RenderParams &p) {
 // Occupancy queries and the launch itself go through it.
 template <int MODE, bool SPEC, bool BVH, int KIND>
 constexpr auto kernel_of() {
-  if constexpr (KIND == KIND_SHADE) {
+  if constexpr (KIND == KIND_TANG) {
+    static_assert(MODE == MODE_ADJ, "the tangent launch is the bounded material adjoint's");
+    return &trace_tan_kernel<SPEC, BVH>;
+  } else if constexpr (KIND == KIND_SHADE) {
     static_assert(shade_mode(MODE), "the shading tables: forwards and bounded adjoints only");
     return &trace_shade_kernel<MODE, SPEC, BVH>;
   } else if constexpr (KIND == KIND_VBMAT) {
@@ -1530,6 +1590,7 @@ constexpr auto kernel_of() {
 // ... and its name, for the IPT_DEBUG_GRID prints.
 constexpr const char *kernel_name(int mode, int kind) {
   return kind == KIND_SHADE  ? "trace_shade_kernel"
+         : kind == KIND_TANG ? "trace_tan_kernel"
          : kind == KIND_VBFWD ? "trace_fwd_views_batch_kernel"
          : kind == KIND_VBMAT ? (mode == MODE_ADJU ? "trace_matu_views_batch_kernel" : "trace_mat_views_batch_kernel")
          : kind == KIND_VFWD ? "trace_fwd_views_kernel"
@@ -1801,6 +1862,8 @@ struct LaunchIO {
   const TriMat *mat = nullptr;  // TriMat table (nullptr: the scene's own; the overrides pass what pack_mat_kernel wrote)
   const float *views = nullptr;  // KIND_VFWD / KIND_VMAT: the views' table
   int nviews = 0;                // KIND_VBFWD / KIND_VBMAT: its entries V (the launch has nscenes / V material sets)
+  const float *tkd = nullptr, *tks = nullptr, *tke = nullptr;  // KIND_TANG: the tangents (nullptr: zero) ...
+  int ntan = 0;                                                // ... and their count; `grad` is the tangent images
   hipStream_t stream = nullptr;
   size_t tail = 0;  // bytes per workgroup behind everything else (16-B aligned; the fused pixel mean's slots, TraceArgs::mean_off)
 };
@@ -1900,6 +1963,7 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const Launch
   else if constexpr (KIND == KIND_VMAT) enqueue(s->tri_emit, io.views);
   else if constexpr (KIND == KIND_VFWD) enqueue(io.views);
   else if constexpr (KIND == KIND_MATG) enqueue(s->tri_emit);
+  else if constexpr (KIND == KIND_TANG) enqueue(s->tri_emit, io.tkd, io.tks, io.tke, io.ntan);
   else enqueue();
   HIP_TRY(hipGetLastError());
   return 0;
@@ -2392,6 +2456,66 @@ static int adjoint_mat_impl(GpuScene *s, const RenderParams &p, const float *kd_
     return launch<MODE_ADJ, KIND_VBMAT>(s, a, lds, io);
   }
   return views_dev ? launch<MODE_ADJ, KIND_VMAT>(s, a, lds, io) : launch<MODE_ADJ, KIND_MATG>(s, a, lds, io);
+}
+
+// The tangent launch: the bounded material adjoint's launch
+// with the tangent tables in the bins' place (tan_lds_doubles) and
+// trace_tan_kernel; tan_dev is n_tangents x band pixels x 3 doubles,
+// accumulated.  Everything is checked before anything is enqueued.
+static int tangent_checks(const GpuScene *s, const RenderParams &p, int n_tangents, bool any_tangent, TraceArgs *args,
+                          size_t *lds_bytes) {
+  // (the call's own arguments first, the frame and the LDS footprint next,
+  // the scene's device last: a host-only scene meets every refusal too)
+  if (n_tangents < 1 || n_tangents > kMaxTangents) {
+    gpu_set_error("material tangents: n_tangents must be in 1..16");
+    return -1;
+  }
+  if (!any_tangent) {
+    gpu_set_error("material tangents: give at least one of the tangent arrays tkd, tks, tke");
+    return -1;
+  }
+  if (p.max_bounces < 0 || p.max_bounces > kMaxAdjBounces) {
+    gpu_set_error("material tangents: give max_bounces in 0..62 (the unbounded estimator is not supported)");
+    return -1;
+  }
+  if (s->host.nT > kMaxAdjTris) {
+    gpu_set_error("material tangents support at most 65535 triangles");
+    return -1;
+  }
+  if (check_frame(s, p)) return -1;
+  if (p.nscenes > 1) {
+    gpu_set_error("material tangents: the scene batch (n_scenes > 1) is not supported");
+    return -1;
+  }
+  bool has_ks = s->has_ks;  // (gpu_upload's; a host-only scene: from its materials)
+  if (!s->on_device)
+    for (const TriMat &m : s->host.mat) has_ks |= (m.flags & MAT_HAS_KS) != 0;
+  const TraceArgs a = adjoint_args(s, p);
+  const size_t fields = (size_t)(has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
+  const size_t lds = tan_lds_doubles(n_tangents, s->host.nT, s->host.nE, has_ks, a.kd_tables != 0) * sizeof(double) +
+                     table_bytes(a) + (size_t)kBlock * sizeof(uint32_t) + (size_t)a.rec_cap * fields * kBlock * sizeof(float);
+  if (lds > 160 * 1024) {
+    gpu_set_error("material tangents: LDS footprint (tangent tables + tables + vertex records) exceeds 160 KiB; lower n_tangents or max_bounces");
+    return -1;
+  }
+  if (check_device(s)) return -1;
+  *args = a;
+  *lds_bytes = lds;
+  return 0;
+}
+
+int gpu_tangent_mat(GpuScene *s, const RenderParams &p, const float *kd_dev, const float *ks_dev, const float *ke_dev,
+                    int n_tangents, const float *tkd_dev, const float *tks_dev, const float *tke_dev, double *tan_dev,
+                    void *stream) {
+  TraceArgs a;
+  size_t lds = 0;
+  if (tangent_checks(s, p, n_tangents, tkd_dev || tks_dev || tke_dev, &a, &lds)) return -1;
+  LaunchMaterials m;
+  if (m.fill(s, &kd_dev, ks_dev, ke_dev, 1, stream)) return -1;
+  LaunchIO io;
+  io.kd = kd_dev, io.grad = tan_dev, io.mat = m.mat, io.stream = (hipStream_t)stream;
+  io.tkd = tkd_dev, io.tks = tks_dev, io.tke = tke_dev, io.ntan = n_tangents;
+  return launch<MODE_ADJ, KIND_TANG>(s, a, lds, io);
 }
 
 // ------------------------------------------------------------ views
@@ -3140,6 +3264,29 @@ int gpu_adjoint_mat_host(GpuScene *s, const RenderParams &p, const float *adj, d
   return accumulate_host(adj, na, grad, ng, [&](const float *a, double *g) {
     return gpu_adjoint_mat(s, p, nullptr, nullptr, nullptr, a, g, nullptr);
   });
+}
+
+int gpu_tangent_mat_host(GpuScene *s, const RenderParams &p, int n_tangents, const float *tkd, const float *tks,
+                         const float *tke, double *tan) {
+  TraceArgs a;
+  size_t lds = 0;
+  if (tangent_checks(s, p, n_tangents, tkd || tks || tke, &a, &lds)) return -1;  // (before anything is allocated)
+  const size_t nt = (size_t)n_tangents * s->host.nT * 3, nout = (size_t)n_tangents * band_rows(p) * p.width * 3;
+  const float *host[3] = {tkd, tks, tke};
+  DevBuf dev[3];
+  for (int i = 0; i < 3; ++i) {
+    if (!host[i]) continue;
+    HIP_TRY(hipMalloc(&dev[i].p, nt * sizeof(float)));
+    HIP_TRY(hipMemcpy(dev[i].p, host[i], nt * sizeof(float), hipMemcpyHostToDevice));
+  }
+  DevBuf out;
+  HIP_TRY(hipMalloc(&out.p, std::max<size_t>(nout, 1) * sizeof(double)));
+  HIP_TRY(hipMemset(out.p, 0, std::max<size_t>(nout, 1) * sizeof(double)));
+  if (gpu_tangent_mat(s, p, nullptr, nullptr, nullptr, n_tangents, (const float *)dev[0].p, (const float *)dev[1].p,
+                      (const float *)dev[2].p, (double *)out.p, nullptr))
+    return -1;
+  HIP_TRY(hipMemcpy(tan, out.p, nout * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int gpu_adjoint_mat_unbounded_host(GpuScene *s, const RenderParams &p, const float *adj, double *grad) {

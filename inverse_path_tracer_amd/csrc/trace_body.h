@@ -14,7 +14,11 @@
 // parameter is the views' table, read by its kernarg offset), and VSETS (with
 // VIEWS: the sets are (material set, view) pairs, DESIGN.md §20 -- the view
 // count V follows the table as one more trailing parameter), and SHADE (the
-// small scenes' shading tables in LDS, DESIGN.md §23: trace_shade_kernel).
+// small scenes' shading tables in LDS, DESIGN.md §23: trace_shade_kernel),
+// and TANG (with MATG at MODE_ADJ: the sweep's terms go, times the tangents'
+// entries of their bins, into per-pixel tangent images instead of the
+// gradient bins, DESIGN.md §24 -- trace_tan_kernel, whose trailing parameters
+// after tri_emit are the three tangent arrays and their count).
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   // scene batch: this workgroup's material set and its place among the set's blocks
@@ -70,6 +74,8 @@
     n_acc = a.grad_slots * 3;
     // material adjoint: [Kd slots][Ks slots (SPEC)][Ke by emitter index] (mat_lds_doubles)
     if (MATG) n_acc = (int)mat_lds_doubles(a.grad_slots, nE, SPEC);
+    // the tangent launch has no bins: its tangent tables take their place
+    if (TANG) n_acc = (int)tan_lds_doubles(karg<int>(sizeof(TraceKernArgs) + 4 * sizeof(void *)), nT, nE, SPEC, a.kd_tables != 0);
   } else if (MODE == MODE_GRAPH && a.lds_edges) {
     n_acc = (int)graph_lds_doubles(nT, nE);
   }
@@ -231,7 +237,29 @@
     cv.stk = reinterpret_cast<uint32_t *>(after) + (tid >> 6) * 8 * a.coop_stride;
     if (kLaneLds) lane_ws = (lds_u32 *)(reinterpret_cast<uint32_t *>(after) + (kBlock / 64) * 8 * a.coop_stride);
   }
-  for (int i = tid; i < n_acc; i += nthr) lds_acc[i] = 0.0;
+  if (!TANG)
+    for (int i = tid; i < n_acc; i += nthr) lds_acc[i] = 0.0;
+  // TANG: the tangents (trailing parameters: tkd, tks, tke, each ntan x nT x 3
+  // floats or nullptr = zero; then ntan).  Small scenes stage them here as
+  // [k][tri] Kd rows, (SPEC) [k][tri] Ks rows -- zero off the lobe mask, whose
+  // rows are never read -- and [k][emitter] Ke rows (only emitters' rows are read)
+  const int ntan = TANG ? karg<int>(sizeof(TraceKernArgs) + 4 * sizeof(void *)) : 0;
+  if (TANG && a.kd_tables) {
+    const float *tkd_p = karg<const float *>(sizeof(TraceKernArgs) + sizeof(void *));
+    const float *tks_p = karg<const float *>(sizeof(TraceKernArgs) + 2 * sizeof(void *));
+    const float *tke_p = karg<const float *>(sizeof(TraceKernArgs) + 3 * sizeof(void *));
+    float *tt = reinterpret_cast<float *>(lds_acc);
+    const int nk = ntan * nT * 3;
+    for (int i = tid; i < nk; i += nthr) tt[i] = tkd_p ? tkd_p[i] : 0.f;
+    if (SPEC)
+      for (int i = tid; i < nk; i += nthr)
+        tt[nk + i] = (tks_p && (mat[(i / 3) % nT].flags & MAT_HAS_KS)) ? tks_p[i] : 0.f;
+    float *te = tt + (SPEC ? 2 : 1) * nk;
+    for (int i = tid; i < ntan * nE * 3; i += nthr) {
+      const int kq = i / (3 * nE), r = i - kq * 3 * nE;
+      te[i] = tke_p ? tke_p[((size_t)kq * nT + emit_tri[r / 3]) * 3 + r % 3] : 0.f;
+    }
+  }
   __syncthreads();
   // fp64 bin updates go to LDS (ds_add_f64) or to global memory by a
   // wave-uniform (GRAPH) or per-lane (ADJ hot set) branch -- never through
@@ -1240,7 +1268,16 @@
         // per-wave LDS word per lane: the round's owner markers
         uint32_t *swl = reinterpret_cast<uint32_t *>(lds_rec) - kBlock + (tid & ~63);
         float wx = 0.f, wy = 0.f, wz = 0.f;  // the owner's adjoint weights dL/dI / spp
-        if (Kf > 0) {
+        uint32_t tlp_lo = 0u, tlp_hi = 0u;   // TANG: the owner's launch-local pixel
+        if (TANG) {  // no adjoint image: dL/dI = 1 at the owner's own pixel
+          if (Kf > 0) {
+            wx = wy = wz = a.rc_spp != 0.f ? a.rc_spp : 1.0f / (float)a.spp;
+            uint64_t lp, sj;
+            item_split(a, witem(), lp, sj);
+            tlp_lo = (uint32_t)lp;
+            tlp_hi = (uint32_t)(lp >> 32);
+          }
+        } else if (Kf > 0) {
           const float *adj = karg<const float *>(offsetof(TraceKernArgs, adj)) +
                              (a.nscenes > 1 ? (size_t)set * a.adj_stride : 0);
           const uint64_t pixel = item_pixel(a, witem());
@@ -1461,6 +1498,13 @@
           // from the lane of the path's task 0 (ADJ: every chunk starts at vertex 0);
           // ADJU: from the owner lane, which carries it like Le (replay chunks start later)
           const int tri0 = kTri0Carry ? tri0c : (MATG ? __shfl(tk, lane - kk) : 0);
+          // TANG: this task's fp32 terms a * g (the adjoint's own products) for
+          // Kd[tk], Ks[tk], Ke[et_k], Ke[tri_0]; t_ks / t_ek / t_e0: the term exists
+          float tg[12];
+#pragma unroll
+          for (int i = 0; i < 12; ++i) tg[i] = 0.f;
+          bool t_ks = false;
+          int t_ek = -1, t_e0 = -1;
           if (valid) {
             V3 dLd = Mk;
             if (esc && rr == 0) {  // the escape's stale re-add weights Ld by M_K = (M_K-1 T_K-1) c_K-1
@@ -1472,6 +1516,22 @@
               const float cpi = div_const<2>(ck);  // ck / kPiF
               gk = mk(gk.x + (cpi * Mk.x) * S.x, gk.y + (cpi * Mk.y) * S.y, gk.z + (cpi * Mk.z) * S.z);
             }
+            if (TANG) {
+              tg[0] = ax * gk.x, tg[1] = ay * gk.y, tg[2] = az * gk.z;
+              if (SPEC && (mat[tk].flags & MAT_HAS_KS)) {
+                V3 gs = mk((dLd.x * lk.x) * sdv, (dLd.y * lk.y) * sdv, (dLd.z * lk.z) * sdv);
+                if (rr > 0 || esc || !fst_o) {
+                  const float cs = ck * si;
+                  gs = mk(gs.x + (cs * Mk.x) * S.x, gs.y + (cs * Mk.y) * S.y, gs.z + (cs * Mk.z) * S.z);
+                }
+                tg[3] = ax * gs.x, tg[4] = ay * gs.y, tg[5] = az * gs.z;
+                t_ks = true;
+              }
+              t_ek = es != 0.f ? tri_emit[etk] : -1;
+              if (t_ek >= 0) tg[6] = ax * ((dLd.x * dj.x) * es), tg[7] = ay * ((dLd.y * dj.y) * es), tg[8] = az * ((dLd.z * dj.z) * es);
+              t_e0 = tri_emit[min(tri0, nT - 1)];
+              if (t_e0 >= 0) tg[9] = ax * dLd.x, tg[10] = ay * dLd.y, tg[11] = az * dLd.z;
+            } else {
             const int sl = a.grad_map ? a.grad_map[tk] : tk;
             const double v[3] = {(double)(ax * gk.x), (double)(ay * gk.y), (double)(az * gk.z)};
             double *grad = karg<double *>(offsetof(TraceKernArgs, grad)) + (VSETS ? (size_t)mset * 9 * a.nT : !VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0);
@@ -1500,6 +1560,83 @@
               if (e0 >= 0) {  // the stale Le, re-added at every vertex: dLd
                 const double v0[3] = {(double)(ax * dLd.x), (double)(ay * dLd.y), (double)(az * dLd.z)};
                 bins_add(true, grad, ke0 + (size_t)e0 * 3, 3, v0);
+              }
+            }
+            }
+          }
+          if (TANG) {
+            // Per tangent k and channel: the task's terms, widened, times the
+            // tangents' entries (fp64), summed over the consecutive task lanes of
+            // ONE PATH by a segmented inclusive scan; the path's last task lane
+            // adds the total to its pixel's entry (one fp64 atomic per path, k and
+            // channel instead of one per task).  Paths that share a pixel are not
+            // combined before the atomics.
+            const uint32_t plo = (uint32_t)__shfl((int)tlp_lo, ow), phi = (uint32_t)__shfl((int)tlp_hi, ow);
+            const bool head = !valid || kk == 0;
+            const int soff = lane - ((int)wave_scan_max(head ? (uint32_t)lane + 1u : 0u) - 1);  // lanes since the segment's first
+            const uint64_t hb = __ballot(head);
+            const bool tail = valid && (lane == 63 || ((hb >> (lane + 1)) & 1ull));
+            uint64_t lp = ((uint64_t)phi << 32) | plo;
+            lp = lp < a.npix ? lp : a.npix - 1;  // (nothing reaches global memory out of bounds)
+            const int nk = ntan * nT * 3;
+            const int tri0t = min(tri0, nT - 1);
+            const gbl_f32 *gkd = nullptr, *gks = nullptr, *gke = nullptr;
+            if (!a.kd_tables) {  // large scenes: the tangents by triangle, from global memory
+              gkd = (const gbl_f32 *)karg<const float *>(sizeof(TraceKernArgs) + sizeof(void *));
+              gks = (const gbl_f32 *)karg<const float *>(sizeof(TraceKernArgs) + 2 * sizeof(void *));
+              gke = (const gbl_f32 *)karg<const float *>(sizeof(TraceKernArgs) + 3 * sizeof(void *));
+            }
+            gbl_f64 *tout = (gbl_f64 *)karg<double *>(offsetof(TraceKernArgs, grad)) + lp * 3;
+            for (int kq = 0; kq < ntan; ++kq) {  // wave-uniform
+              double c[3] = {0.0, 0.0, 0.0};
+              if (valid) {
+                if (a.kd_tables) {
+                  const lds_f32 *tt = (const lds_f32 *)lds_acc;
+                  const lds_f32 *q = tt + ((size_t)kq * nT + tk) * 3;
+#pragma unroll
+                  for (int i = 0; i < 3; ++i) c[i] = (double)tg[i] * (double)q[i];
+                  if (SPEC && t_ks) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] += (double)tg[3 + i] * (double)q[nk + i];
+                  }
+                  const lds_f32 *te = tt + (SPEC ? 2 : 1) * nk + (size_t)kq * nE * 3;
+                  if (t_ek >= 0) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] += (double)tg[6 + i] * (double)te[t_ek * 3 + i];
+                  }
+                  if (t_e0 >= 0) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] += (double)tg[9 + i] * (double)te[t_e0 * 3 + i];
+                  }
+                } else {
+                  const size_t r = ((size_t)kq * nT + tk) * 3;
+                  if (gkd) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] = (double)tg[i] * (double)gkd[r + i];
+                  }
+                  if (SPEC && gks && t_ks) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] += (double)tg[3 + i] * (double)gks[r + i];
+                  }
+                  if (gke && t_ek >= 0) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] += (double)tg[6 + i] * (double)gke[((size_t)kq * nT + etk) * 3 + i];
+                  }
+                  if (gke && t_e0 >= 0) {
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) c[i] += (double)tg[9 + i] * (double)gke[((size_t)kq * nT + tri0t) * 3 + i];
+                  }
+                }
+              }
+              for (int d = 1; __ballot(soff >= d); d <<= 1) {  // (soff <= 63: at most six steps)
+                const double u0 = __shfl_up(c[0], d), u1 = __shfl_up(c[1], d), u2 = __shfl_up(c[2], d);
+                if (soff >= d) c[0] += u0, c[1] += u1, c[2] += u2;
+              }
+              if (tail) {
+                gbl_f64 *o = tout + (size_t)kq * a.npix * 3;
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+                  if (c[i] != 0.0) __hip_atomic_fetch_add(o + i, c[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               }
             }
           }
@@ -1563,7 +1700,7 @@
 
   if (!is_fwd<MODE>()) {
     __syncthreads();
-    if (n_acc > 0) {
+    if (!TANG && n_acc > 0) {
       double *dstp = is_adj<MODE>() ? karg<double *>(offsetof(TraceKernArgs, grad)) + (VSETS ? (size_t)mset * 9 * a.nT : !VIEWS && a.nscenes > 1 ? (size_t)set * (MATG ? 9 : 3) * a.nT : 0)
                                     : edges;
       const int nb5 = (nT + 1) * nT * kEdgeL;

@@ -467,6 +467,74 @@ def optimize(tasks: List[SceneTask], width: int, height: int, spp: int, max_boun
     return m.shared
 
 
+def gauss_newton_materials(scene: Scene, target_hdr, groups, width: int, height: int, spp: int, max_bounces: int,
+                           seed: int, steps: int, damping: float = 0.0, tangent_seed: Optional[int] = None):
+    """Gauss-Newton on a few tied material parameters, with the Jacobian from
+    the tangent launch.
+
+    `groups` is a list of (block, rows), block in ("kd", "ks", "ke"): the rows
+    of a group share ONE value per channel (started from the scene's value in
+    the group's first row), K = len(groups) <= 16.  A step is one
+    ipt_render_mat_dev launch and one ipt_tangent_mat_dev launch with one
+    indicator tangent per group; then per channel c, with A the K x pixels
+    matrix of the tangents' channel c and r = target - I, delta solves
+    (A A^T + damping I) delta = A r (least squares when singular), and is added
+    to the groups' rows.  The scene's own values are not changed.
+
+    `tangent_seed` None differentiates the forward's own paths (the exact
+    Jacobian of the returned image).  When the target is a noisy render on an
+    independent sample stream, DESIGN.md §5.4 applies: with the forward's own
+    samples E[(I - T) dI] = (E[I] - T) E[dI] + Cov(I, dI), and the covariance
+    term biases the right side A r (towards darker albedo; at the truth it
+    measured 7x the remaining noise at 4 spp).  Give `tangent_seed` an
+    independent stream to remove it -- one whose seeds differ from the
+    forward's in the LOW 32 bits, e.g. seed + W*H*spp: curand_init hashes a
+    seed's halves separately, and seeds equal modulo 2^32 stay correlated (a
+    bias of 14% of the same-stream one).  With a target rendered at the truth on the SAME seed
+    the residual is exactly 0 there and the forward's own paths are right.
+
+    Returns the groups' values after each step, (steps, K, 3) float64."""
+    K = len(groups)
+    if not 1 <= K <= 16:
+        raise ValueError("gauss_newton_materials takes 1..16 groups, got %d" % K)
+    names = ("kd", "ks", "ke")
+    host = scene.material_params()[:3]
+    dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in host]
+    tang = [None, None, None]
+    idx, val = [], np.zeros((K, 3), np.float64)
+    for k, (block, rows) in enumerate(groups):
+        if block not in names:
+            raise ValueError("group block must be one of %s, got %r" % (names, block))
+        b = names.index(block)
+        r = torch.as_tensor(np.asarray(list(rows), np.int64), device="cuda")
+        if r.numel() == 0 or int(r.min()) < 0 or int(r.max()) >= scene.nT:
+            raise ValueError("group %d: rows must be in 0..%d" % (k, scene.nT - 1))
+        if tang[b] is None:
+            tang[b] = torch.zeros((K, scene.nT, 3), device="cuda", dtype=torch.float32)
+        tang[b][k, r] = 1.0
+        idx.append((b, r))
+        val[k] = host[b][int(r[0])]
+    target = torch.as_tensor(np.asarray(target_hdr, np.float32) if not torch.is_tensor(target_hdr) else target_hdr,
+                             device="cuda").reshape(height, width, 3).double()
+    history = np.zeros((steps, K, 3), np.float64)
+    for s in range(steps):
+        for k, (b, r) in enumerate(idx):
+            dev[b][r] = torch.as_tensor(val[k], dtype=torch.float32, device="cuda")
+        with torch.no_grad():
+            img = torch_ops.render_materials(scene, dev[0], dev[1], dev[2], width, height, spp, max_bounces, seed)
+        tan = torch_ops.tangent_materials(scene, dev[0], dev[1], dev[2], tang[0], tang[1], tang[2], width, height, spp,
+                                          max_bounces, seed if tangent_seed is None else int(tangent_seed))
+        res = (target - img.double()).reshape(-1, 3)
+        A = tan.reshape(K, -1, 3)
+        for c in range(3):
+            Ac = A[:, :, c]
+            n = (Ac @ Ac.T).cpu().numpy() + damping * np.eye(K)
+            rhs = (Ac @ res[:, c]).cpu().numpy()
+            val[:, c] += np.linalg.lstsq(n, rhs, rcond=None)[0]
+        history[s] = val
+    return history
+
+
 def _flush_losses(pending):
     """Move the pending per-scene losses to the tasks' histories (one copy)."""
     if pending:

@@ -300,6 +300,36 @@ class Scene:
                                              g.ctypes.data_as(N.dp)), "adjoint_materials")
         return g[0], g[1], g[2]
 
+    def tangent_materials(self, tkd, tks, tke, width, height, spp, max_bounces, seed=0, row_begin=0, row_end=None,
+                          row_step=1):
+        """Forward-mode derivatives of the HDR image along K directions in
+        material space, from ONE launch (ipt_tangent_mat_host; the paths are
+        traced once): tkd, tks, tke are (K, nT, 3) host arrays -- (nT, 3) means
+        K = 1 -- or None (zero; at least one is given), 1 <= K <= 16.  Returns
+        (K, rows, W, 3) float64: entry [k, p, c] is <``adjoint_materials`` under
+        the one-hot adjoint image at p, tangent k> in channel c, to fp64
+        summation order.  The scene's own material values; bounded estimator
+        only.  tks rows outside lobe_mask and tke rows outside emitter_mask are
+        ignored."""
+        p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+        t, K = [], None
+        for name, v in (("tkd", tkd), ("tks", tks), ("tke", tke)):
+            if v is not None:
+                v = np.ascontiguousarray(np.asarray(v, np.float32))
+                if v.ndim == 2:
+                    v = v[None]
+                if v.ndim != 3 or v.shape[1:] != (self.nT, 3) or (K is not None and v.shape[0] != K):
+                    raise ValueError("%s must be (K, nT=%d, 3) with one K for all, got %s" % (name, self.nT, v.shape))
+                K = v.shape[0]
+            t.append(v)
+        if K is None:
+            raise N.NativeError("material tangents: give at least one of the tangent arrays tkd, tks, tke")
+        out = np.zeros((K, p.rows, width, 3), np.float64)
+        N.check(N.lib().ipt_tangent_mat_host(self.handle, C.byref(p), K,
+                                             *[v.ctypes.data_as(N.fp) if v is not None else None for v in t],
+                                             out.ctypes.data_as(N.dp)), "tangent_materials")
+        return out
+
     def adjoint_materials_unbounded(self, adj, width, height, spp, seed=0, row_begin=0, row_end=None, row_step=1):
         """``adjoint_materials`` for the reference's own estimator (no bounce
         cap, paths end by Russian roulette or a miss): three (nT, 3) float64

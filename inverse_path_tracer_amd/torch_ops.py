@@ -209,6 +209,67 @@ class _MaterialsFn(torch.autograd.Function):
                for i, t in enumerate(ctx.mat)]
         return out[0], out[1], out[2], None, None, None, None, None, None
 
+    @staticmethod
+    def jvp(ctx, tkd, tks, tke, *_):
+        """Forward-mode AD (torch.autograd.forward_ad): ONE tangent launch with
+        K = 1 at the forward's own seed, cast once to float32.  Only
+        ``render_materials`` has a tangent kernel."""
+        route, scene, views, params, lead, stride = ctx.call
+        if route.name != "render_materials":
+            raise N.NativeError("forward-mode AD is not supported by %s; render_materials (one material set, the "
+                                "scene's own camera, max_bounces in 0..62) is the supported op" % route.name)
+        first = next(t for t in ctx.mat if t is not None)
+        # an input without a tangent, or one that is not given, contributes nothing
+        t = [None if (v is None or m is None) else v.detach().contiguous().float()
+             for v, m in zip((tkd, tks, tke), ctx.mat)]
+        if all(v is None for v in t):
+            return torch.zeros((params.rows, params.width, 3), device=first.device, dtype=torch.float32)
+        return _tangent_launch(scene, params, ctx.mat, t, 1, first.device)[0].float()
+
+
+def _tangent_launch(scene, params: N.Params, mats, tangents, K: int, device) -> torch.Tensor:
+    """ipt_tangent_mat_dev on torch's current stream: (K, rows, W, 3) float64."""
+    out = torch.zeros((K, params.rows, params.width, 3), device=device, dtype=torch.float64)
+    N.check(N.lib().ipt_tangent_mat_dev(scene.handle, C.byref(params), *[_ptr(t) for t in mats], K,
+                                        *[_ptr(t) for t in tangents], out.data_ptr(), _stream(device)),
+            "ipt_tangent_mat_dev")
+    return out
+
+
+def tangent_materials(scene: Scene, kd, ks, ke, tkd, tks, tke, width: int, height: int, spp: int, max_bounces=4,
+                      seed: int = 0, row_begin: int = 0, row_end=None, row_step: int = 1) -> torch.Tensor:
+    """Tangent images of ``render_materials``: K directions in material space
+    -> a float64 CUDA tensor (K, rows, W, 3) from ONE launch
+    (ipt_tangent_mat_dev; the paths are traced once, however many directions).
+    kd, ks, ke: (nT, 3) CUDA tensors or None (the scene's own values); tkd,
+    tks, tke: (K, nT, 3) CUDA tensors -- (nT, 3) means K = 1 -- or None (zero;
+    at least one is given), 1 <= K <= 16.  Entry [k, p, c] is the derivative of
+    pixel p's channel c of the HDR mean along direction k under the forward's
+    own paths: <the material adjoint's gradient under the one-hot adjoint image
+    at p, tangent k>, to fp64 summation order.  tks rows outside
+    ``scene.lobe_mask`` and tke rows outside ``scene.emitter_mask`` are ignored.
+    Runs on torch's current stream; no autograd graph.  Bounded estimator only
+    (max_bounces 0..62)."""
+    given = [t for t in (tkd, tks, tke) if t is not None]
+    if not given:
+        raise N.NativeError("material tangents: give at least one of the tangent arrays tkd, tks, tke")
+    K = given[0].shape[0] if given[0].dim() == 3 else 1
+    for t in given:
+        if tuple(t.shape) not in ((K, scene.nT, 3),) + (((scene.nT, 3),) if K == 1 else ()):
+            raise ValueError("tkd, tks, tke must be (K=%d, nT=%d, 3), got %s" % (K, scene.nT, tuple(t.shape)))
+    for t in (kd, ks, ke):
+        if t is not None and tuple(t.shape) != (scene.nT, 3):
+            raise ValueError("kd, ks, ke must be (nT=%d, 3), got %s" % (scene.nT, tuple(t.shape)))
+    for t in (kd, ks, ke, tkd, tks, tke):  # raw pointers go to the native call: all on one GPU
+        if t is not None and (not t.is_cuda or t.device != given[0].device):
+            raise ValueError("tangent_materials needs CUDA tensors on one device, got %s and %s" %
+                             (t.device, given[0].device))
+    if max_bounces is None or max_bounces < 0:
+        raise N.NativeError("material tangents: give max_bounces in 0..62 (the unbounded estimator is not supported)")
+    p = N.make_params(width, height, spp, max_bounces, seed, row_begin, row_end, row_step)
+    c = [None if t is None else t.detach().contiguous().float() for t in (kd, ks, ke, tkd, tks, tke)]
+    return _tangent_launch(scene, p, c[:3], c[3:], K, given[0].device)
+
 
 def _materials(name, scene, views, kd, ks, ke, width, height, spp, max_bounces, seed, seed_stride, adjoint_seed,
                rows=(0, None, 1)):
