@@ -67,7 +67,8 @@ void setMaterials(void *scenePtr, float *materials);
  * share); images and sample buffers hold those rows, in that order.
  * ABI 2 added row_step; ABI 3 dropped the quantised-node export of
  * ipt_scene_export_wide; ABI 4 added ipt_debug_fail_launches; ABI 5 added
- * ipt_debug_adju_ring (ipt_abi_version).  Bindings must check the version
+ * ipt_debug_adju_ring; ABI 6 added ipt_debug_last_launch
+ * (ipt_abi_version).  Bindings must check the version
  * before passing this struct. */
 typedef struct ipt_params {
   int32_t width, height, spp, max_bounces;
@@ -78,7 +79,7 @@ typedef struct ipt_params {
 
 const char *ipt_last_error(void);
 void ipt_clear_error(void);
-int ipt_abi_version(void);            /* 5 */
+int ipt_abi_version(void);            /* 6 */
 int ipt_device_count(void);
 /* Diagnostic: bitwise self-test of the kernels' in-range sqrt/division cores
  * against the IEEE operations over n random operands per test; counts[8]
@@ -95,6 +96,31 @@ void ipt_debug_fail_launches(int n);
  * loaded that read a small scene's shading data from the LDS tables (the
  * trace_shade_kernel instances).  No reference counterpart. */
 int ipt_debug_shade_launches(void);
+/* Diagnostic (tests): the numbers the host decided for the last trace launch
+ * of the process, so that a test can assert which kernel instance and which
+ * LDS layout a scene got.  Writes the first n of these int32 fields to out and
+ * returns how many fields there are (18):
+ *    0 launches recorded since the library was loaded
+ *    1 MODE  (0 forward, 1 bounded adjoint, 2 graph, 3 unbounded adjoint,
+ *            4 forward with the fused pixel mean, 5 six-wave bounded adjoint)
+ *    2 SPEC  (the Phong-lobe instance)      3 BVH (1) or the pair loop (0)
+ *    4 KIND  (0 trace, 1 material adjoint, 2 batch forward, 3 views forward,
+ *            4 views adjoint, 5 view-sets forward, 6 view-sets adjoint,
+ *            7 shading tables in LDS, 8 tangents)
+ *    5 kd_tables: Kd and Kd/pi (and a tangent launch's tangents) in LDS
+ *    6 small_pairs: bit 0 unrolled pair loop, bit 1 shading tables in LDS
+ *    7 grad_slots: gradient bins in LDS (nT: all of them)
+ *    8 bvh_wide_lds: wide BVH nodes staged in LDS (0: none)
+ *    9 rec_lds: unbounded adjoint, ring slots per lane in LDS
+ *   10 lds_edges: graph bins in LDS
+ *   11 LDS bytes per workgroup             12 rec_cap (vertex records per lane)
+ *   13 bvh_big_lds: large pairs copied to LDS
+ *   14 BVH emitter records in LDS           15 grid (workgroups)
+ *   16 nT   17 nE
+ * The record is taken just before the kernel is enqueued; a launch that was
+ * refused, failed earlier or traced no sample leaves it unchanged.  No
+ * reference counterpart. */
+int ipt_debug_last_launch(int32_t *out, int n);
 /* Diagnostic (tests): the unbounded adjoint's record ring at reduced sizes --
  * pool_chunks 16-slot chunks per wave pool (1..63) and lds_slots LDS slots
  * per lane (>= 1); 0 restores the launch's own choice.  Small pools make

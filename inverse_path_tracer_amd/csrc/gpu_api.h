@@ -130,6 +130,7 @@ int gpu_closest_hit_host(GpuScene *s, int64_t n, const float *org, const float *
 
 int gpu_device_count();
 int gpu_selftest_math(uint64_t n, uint64_t seed, uint64_t *counts);  // 8 mismatch counters
+int gpu_debug_last_launch(int32_t *out, int n);  // host-decided numbers of the last trace launch (include/ipt.h)
 int gpu_debug_shade_launches();  // trace launches so far that ran a trace_shade_kernel instance
 void gpu_debug_fail_launches(int n);  // the next n trace launches fail before their kernel is enqueued
 void gpu_debug_adju_ring(int pool_chunks, int lds_slots);  // unbounded adjoint ring sizes (0: default)

@@ -58,6 +58,19 @@ void gpu_debug_fail_launches(int n) { g_fail_launches.store(n > 0 ? n : 0); }
 // ran a trace_shade_kernel instance (the shading tables in LDS)
 static std::atomic<int> g_shade_launches{0};
 int gpu_debug_shade_launches() { return g_shade_launches.load(); }
+// ipt_debug_last_launch(out, n): the host-decided numbers of the process's
+// last trace launch (what IPT_DEBUG_GRID prints, kept in every build) -- the
+// tests' way to assert which kernel instance and which LDS layout a scene got.
+// Field order: include/ipt.h.  Written under a lock just before the kernel is
+// enqueued; word 0 counts the launches recorded since the library was loaded.
+constexpr int kLastLaunchFields = 18;
+static std::mutex g_last_launch_mu;
+static int32_t g_last_launch[kLastLaunchFields] = {0};
+int gpu_debug_last_launch(int32_t *out, int n) {
+  std::lock_guard<std::mutex> lk(g_last_launch_mu);
+  for (int i = 0; i < n && i < kLastLaunchFields; ++i) out[i] = g_last_launch[i];
+  return kLastLaunchFields;
+}
 // ipt_debug_adju_ring(chunks, slots): the unbounded adjoint's pool chunks per
 // wave and LDS slots per lane forced small (0: the launch's choice) -- the
 // tests' way to run the empty-pool and short-ring paths
@@ -1952,6 +1965,15 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const Launch
                  b.chunk_big_n, b.grabs, b.group, b.rec_cap, b.rec_lds, b.pool_chunks, (unsigned long long)b.grec_stride,
                  b.grad_slots, b.bvh_wide_lds, b.bvh_big_lds, b.coop_stride, b.mean_off, b.mean_wstride, b.nslots,
                  b.mat_stride, b.kd_tables, b.small_pairs, b.sample_major);
+  {  // ipt_debug_last_launch
+    const int32_t rec[kLastLaunchFields] = {
+        0, MODE, (int)SPEC, (int)BVH, KIND, b.kd_tables, b.small_pairs, b.grad_slots, b.bvh_wide_lds, b.rec_lds, b.lds_edges,
+        (int32_t)lds, b.rec_cap, b.bvh_big_lds, BVH && emit_lds_bytes(b.nE) ? 1 : 0, grid, b.nT, b.nE};
+    std::lock_guard<std::mutex> lk(g_last_launch_mu);
+    const int32_t count = g_last_launch[0] + 1;
+    std::memcpy(g_last_launch, rec, sizeof rec);
+    g_last_launch[0] = count;
+  }
   // the parameters every trace kernel takes, then its own trailing ones
   auto enqueue = [&](auto... trailing) {
     hipLaunchKernelGGL((kernel_of<MODE, SPEC, BVH, KIND>()), dim3(grid), dim3(kBlock), lds, st, b, s->isect, s->pairs,
@@ -2490,12 +2512,31 @@ static int tangent_checks(const GpuScene *s, const RenderParams &p, int n_tangen
   bool has_ks = s->has_ks;  // (gpu_upload's; a host-only scene: from its materials)
   if (!s->on_device)
     for (const TriMat &m : s->host.mat) has_ks |= (m.flags & MAT_HAS_KS) != 0;
-  const TraceArgs a = adjoint_args(s, p);
+  TraceArgs a = adjoint_args(s, p);
   const size_t fields = (size_t)(has_ks ? kRecFieldsSpec : kRecFieldsDiffuse);
-  const size_t lds = tan_lds_doubles(n_tangents, s->host.nT, s->host.nE, has_ks, a.kd_tables != 0) * sizeof(double) +
-                     table_bytes(a) + (size_t)kBlock * sizeof(uint32_t) + (size_t)a.rec_cap * fields * kBlock * sizeof(float);
-  if (lds > 160 * 1024) {
-    gpu_set_error("material tangents: LDS footprint (tangent tables + tables + vertex records) exceeds 160 KiB; lower n_tangents or max_bounces");
+  // The launch's bytes before the BVH carve-out, and with the least the BVH
+  // instance adds behind them (launch_bvh_pick's last option: nothing
+  // staged), so that a launch accepted here is resident.
+  size_t lds = 0;
+  auto footprint = [&]() {
+    lds = tan_lds_doubles(n_tangents, s->host.nT, s->host.nE, has_ks, a.kd_tables != 0) * sizeof(double) + table_bytes(a) +
+          (size_t)kBlock * sizeof(uint32_t) + (size_t)a.rec_cap * fields * kBlock * sizeof(float);
+    if (!use_bvh(s)) return lds;
+    TraceArgs c = a;
+    return bvh_lds_offset(bvh_lds(s, c, lds, false, false));
+  };
+  // The tangent tables go with the kd tables (trace_body.h).  Where both do
+  // not fit beside the vertex records, the launch leaves them in global
+  // memory -- the path every scene past kMaxTableTris takes -- so that a scene
+  // is never refused a K that a larger one gets.  What is
+  // left then does not depend on n_tangents.
+  size_t all = footprint();
+  if (all > 160 * 1024 && a.kd_tables) {
+    a.kd_tables = 0;
+    all = footprint();
+  }
+  if (all > 160 * 1024) {
+    gpu_set_error("material tangents: LDS footprint (tables + vertex records) exceeds 160 KiB; lower max_bounces");
     return -1;
   }
   if (check_device(s)) return -1;

@@ -24,6 +24,18 @@ CLUTTER_SCENE = SPHERE_SCENE + [
 ]
 
 
+def _recs(name, tmp):
+    """Object records by name ("ladder:<rung>": a generated scene of tests/scene_ladder.py, written under tmp)."""
+    import scene_ladder as SL
+    from conftest import NORTHSTAR
+
+    return SL.named(tmp, name, {"sphere": SPHERE_SCENE, "clutter": CLUTTER_SCENE, "cornell": CORNELL, "scene0": SCENE0,
+                                "northstar": NORTHSTAR})
+
+
+LADDER_BVH = ["ladder:64-2-0", "ladder:300-22-100", "ladder:513-2-0"]
+
+
 def _tree(nodes):
     """parent links: leaf pair ranges and node parents from the export."""
     kids = np.ascontiguousarray(nodes[:, 12:14]).view(np.int32)
@@ -149,8 +161,9 @@ def _r_all(tris, cam_origin):
     return float(max(v, np.abs(cam_origin).max()) + 1.0)
 
 
-@pytest.mark.parametrize("recs", [SPHERE_SCENE, CLUTTER_SCENE], ids=["sphere", "clutter"])
-def test_acceptance_inside_every_ancestor_box(oracle, recs):
+@pytest.mark.parametrize("name", ["sphere", "clutter"] + LADDER_BVH)
+def test_acceptance_inside_every_ancestor_box(oracle, tmp_path, name):
+    recs = _recs(name, tmp_path)
     P, Q = product_scene(recs, device=False), oracle.OracleScene(recs)
     tris = P.triangles()
     cam = P.camera()
@@ -238,7 +251,16 @@ def _traverse(nodes, pairs, big, kids, o, d, oracle_scene):
 
 
 def test_emulated_traversal_matches_oracle_closest_hit(sphere_scene):
-    P, Q = sphere_scene
+    _emulated_traversal_matches(*sphere_scene)
+
+
+@pytest.mark.parametrize("name", LADDER_BVH)
+def test_emulated_traversal_matches_oracle_closest_hit_on_generated_scenes(oracle, tmp_path, name):
+    recs = _recs(name, tmp_path)
+    _emulated_traversal_matches(product_scene(recs, device=False), oracle.OracleScene(recs))
+
+
+def _emulated_traversal_matches(P, Q):
     nodes, pairs, big = P.export_bvh()
     kids, _, _ = _tree(nodes)
     tris = P.triangles()
@@ -320,14 +342,14 @@ def _shadow_rays(tris, n, rng, edge_frac=0.3):
     return O.astype(np.float32), D.astype(np.float32), emit[e].astype(np.int32), src.astype(np.int32), e, dist
 
 
-@pytest.mark.parametrize("which", ["cornell", "scene0"])
-def test_shadow_occluder_masks_are_conservative(oracle, which):
+@pytest.mark.parametrize("which", ["cornell", "scene0", "ladder:32-16-0"])
+def test_shadow_occluder_masks_are_conservative(oracle, tmp_path, which):
     """bvh.cpp shadow_occluder_masks: whenever the oracle's closest hit of a
     shadow ray from a point on triangle s towards emitter e is an occluder
     (not the target, no farther than the target point), that occluder's pair
     is in mask[s, e]; the emitter's own
     pair is always in; and the masks do leave pairs out."""
-    recs = CORNELL if which == "cornell" else SCENE0
+    recs = _recs(which, tmp_path)
     P = product_scene(recs, device=False)
     Q = oracle.OracleScene(recs)
     tris = P.triangles()

@@ -987,15 +987,17 @@ def test_bvh_renders_equal_brute_force_and_oracle(oracle):
     P.set_accel(N.ACCEL_AUTO)
 
 
-@pytest.mark.parametrize("which", ["cornell", "scene0"])
-def test_culled_shadow_query_equals_brute_force(which):
+@pytest.mark.parametrize("which", ["cornell", "scene0", "ladder:31-2-0", "ladder:32-16-0"])
+def test_culled_shadow_query_equals_brute_force(which, tmp_path):
     """Small scenes: the megakernel's culled shadow cast (target first, pairs
     skipped by acceptance box over [1e-2, t_target]) answers "closest hit is
     the target, at t" exactly as the full brute-force loop, for shadow rays
     from points on every triangle (grazing ones included) and from random
     points inside the scene box, towards points on the emitters (edges and
     corners included)."""
-    P = product_scene(CORNELL if which == "cornell" else SCENE0)
+    from test_bvh import _recs
+
+    P = product_scene(_recs(which, tmp_path))
     tris = P.triangles()
     emit = np.nonzero(tris[:, 56] >= 0)[0]
     assert len(emit) >= 1
@@ -1030,15 +1032,17 @@ def test_culled_shadow_query_equals_brute_force(which):
     P.close()
 
 
-@pytest.mark.parametrize("which", ["cornell", "scene0"])
-def test_culled_path_cast_equals_brute_force(oracle, which):
+@pytest.mark.parametrize("which", ["cornell", "scene0", "ladder:31-2-0", "ladder:32-16-0"])
+def test_culled_path_cast_equals_brute_force(oracle, which, tmp_path):
     """Small scenes: the megakernel's culled path cast (a lane tests only the
     pairs whose acceptance box its ray enters, per-lane from the LDS copy)
     returns the full brute-force loop's hit bit-for-bit (index and t), and the
     oracle's: rays from points on every triangle in all directions (grazing
     included), adversarial rays at vertices and edges from the camera, and
     random rays inside the scene box."""
-    recs = CORNELL if which == "cornell" else SCENE0
+    from test_bvh import _recs
+
+    recs = _recs(which, tmp_path)
     P = product_scene(recs)
     tris = P.triangles()
     rng = np.random.RandomState(31)
@@ -1072,8 +1076,8 @@ def test_culled_path_cast_equals_brute_force(oracle, which):
     P.close()
 
 
-@pytest.mark.parametrize("which", ["northstar", "clutter"])
-def test_tree_entry_culls_equal_brute_force(which):
+@pytest.mark.parametrize("which", ["northstar", "clutter", "ladder:300-22-100"])
+def test_tree_entry_culls_equal_brute_force(which, tmp_path):
     """BVH scenes: the tree's entry tests (bvh.cpp tree_cull) -- the bounding
     sphere of its triangles' acceptance regions and the source-plane skip of
     rays leaving a triangle with every tree triangle behind its plane (the
@@ -1083,10 +1087,9 @@ def test_tree_entry_culls_equal_brute_force(which):
     skip's threshold; rays from the room towards points just outside and
     inside the tree's bounding sphere; shadow rays with their source."""
     from inverse_path_tracer_amd import _native as N
-    from conftest import NORTHSTAR
-    from test_bvh import CLUTTER_SCENE, _shadow_rays
+    from test_bvh import _recs, _shadow_rays
 
-    P = product_scene(NORTHSTAR if which == "northstar" else CLUTTER_SCENE)
+    P = product_scene(_recs(which, tmp_path))
     assert P.bvh_info()["accel"] == "bvh"
     tris = P.triangles()
     v = tris[:, 0:9].reshape(-1, 3, 3).astype(np.float64)
@@ -1210,18 +1213,17 @@ def test_closest_hit_with_non_unit_directions(which, scale):
     P.close()
 
 
-@pytest.mark.parametrize("which", ["cornell", "scene0", "northstar"])
-def test_masked_shadow_query_equals_brute_force(which):
+@pytest.mark.parametrize("which", ["cornell", "scene0", "northstar", "ladder:31-2-0", "ladder:32-16-0"])
+def test_masked_shadow_query_equals_brute_force(which, tmp_path):
     """The megakernel's shadow cast with the static potential-occluder mask of
     its (source triangle, emitter) answers "closest hit is the target, at t"
     exactly as the full brute-force loop: origins on every triangle (shadow
     rays along the light's own plane included), targets on the emitters near
     their edges and corners (ties with the coplanar ceiling)."""
     from inverse_path_tracer_amd import _native as N
-    from conftest import NORTHSTAR
-    from test_bvh import _shadow_rays
+    from test_bvh import _recs, _shadow_rays
 
-    P = product_scene({"cornell": CORNELL, "scene0": SCENE0, "northstar": NORTHSTAR}[which])
+    P = product_scene(_recs(which, tmp_path))
     O, D, tg, src, _, _ = _shadow_rays(P.triangles(), 400000, np.random.RandomState(23))
     src[::7] = -1  # no mask for some: the plain culled cast
     tc, ic = P.shadow_hit(O, D, tg, src)  # BVH scenes: the large-triangle pre-pass with the masks

@@ -37,7 +37,7 @@ def test_declared_exported_and_bound():
         assert args[2] == "int n_scenes" and args[3] == "uint64_t seed_stride" and args[-1] == "void *stream"
         assert hasattr(raw, name) and hasattr(N.lib(), name)
     assert "double *grad_dev" in re.search(r"ipt_adjoint_mat_batch_dev\s*\(([^;]*)\)", header).group(1)
-    assert N.lib().ipt_abi_version() == 5 == N.ABI_VERSION
+    assert N.lib().ipt_abi_version() == 6 == N.ABI_VERSION
 
 
 def test_bad_arguments_and_host_only_scene(scene):

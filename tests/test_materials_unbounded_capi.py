@@ -44,7 +44,7 @@ def test_declared_exported_and_bound():
     assert N.SIGNATURES[NAMES[1]] == N.SIGNATURES["ipt_adjoint_mat_host"]
     dev = re.search(r"ipt_adjoint_mat_unbounded_dev\s*\(([^;]*)\)", header).group(1)
     assert "double *grad_dev" in dev and dev.strip().endswith("void *stream")
-    assert N.lib().ipt_abi_version() == 5 == N.ABI_VERSION
+    assert N.lib().ipt_abi_version() == 6 == N.ABI_VERSION
     assert callable(getattr(Scene, "adjoint_materials_unbounded"))
 
 

@@ -22,6 +22,7 @@ import collections
 import numpy as np
 import pytest
 
+import scene_ladder as SL
 import test_gpu_materials_unbounded as MU
 from conftest import CORNELL, CUBE_OBJ, SCENE0
 from test_gpu_materials import (H_KS, REL_KE, TOL_KS_ENTRY, bits, dot64, oracle_hdr, pos_adj, scene_a, scene_b,
@@ -382,12 +383,21 @@ def _scene(oracle, tmp, name):
         return oracle.OracleScene(scene_b(tmp, tag="g"))
     if name == "glow":
         return oracle.OracleScene(glow_records(tmp))
+    if name.startswith("ladder:"):
+        return oracle.OracleScene(SL.records(tmp, name[len("ladder:"):]))
     return oracle.OracleScene(MU.sphere_records(tmp))
 
 
 GPU_FRAMES = ([("B", f, 1) for f in B_BOUNDED + B_UNBOUNDED] + [("glow", f, 1) for f in GLOW] +
               [("sphere", f, 1) for f in SPHERE + SPHERE_WIDE] + [("B", f, N_SETS) for f in BATCH_B] +
               [("glow", f, N_SETS) for f in BATCH_GLOW])
+# the generated scenes of tests/test_gpu_scene_ladder.py (scene_ladder.py): the material adjoint's two frames on every
+# rung with emitting or lobe shards, the 3-set batch, and the tangent rungs' frame
+LADDER = {n: tuple(F(*f) for f in SL.mat_frames(n)) for n in SL.MAT_RUNGS}  # (bounded, unbounded)
+LADDER_TAN = {n: F(*f) for n, (_, f, _) in SL.TANGENTS.items()}
+GPU_FRAMES += ([("ladder:" + n, f, 1) for n in SL.MAT_RUNGS for f in LADDER[n]] +
+               [("ladder:" + n, LADDER[n][0], N_SETS) for n in SL.MAT_BATCH_RUNGS] +
+               [("ladder:" + n, f, 1) for n, f in LADDER_TAN.items()])
 _SCENES = {}
 
 

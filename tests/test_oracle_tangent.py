@@ -17,6 +17,7 @@ import time
 import numpy as np
 import pytest
 
+import scene_ladder as SL
 import test_oracle_materials as OM
 from conftest import ASSETS, CORNELL, product_scene
 from test_gpu_materials import scene_b
@@ -26,12 +27,16 @@ NAMES = ("ipt_tangent_mat_dev", "ipt_tangent_mat_host")
 COVERAGE = 0.85  # A_ref > 0 in at least this share of a frame's entries
 # (scene, frame, K) of the GPU file's comparisons with the oracle
 GPU_FRAMES = [("B", f, 3) for f in OM.B_BOUNDED] + [("glow", OM.GLOW[0], 16), ("sphere", OM.SPHERE[0], 2)]
+# ... and of tests/test_gpu_scene_ladder.py: the generated scenes (scene_ladder.py)
+GPU_FRAMES += [("ladder:" + n, OM.LADDER_TAN[n], K) for n, (K, _, _) in SL.TANGENTS.items()]
 SCENE_A = CORNELL + [((0, -1.5, 4), (0, 0.3, 0), (1, 1, 1), os.path.join(ASSETS, "phong", "cube_phong.obj"),
                       os.path.join(ASSETS, "phong", "cube_phong.mtl"))]
 
 
 # ------------------------------------------------------------------ shared with the GPU file
 def records(tmp, name):
+    if name.startswith("ladder:"):
+        return SL.records(tmp, name[len("ladder:"):])
     return {"B": lambda: scene_b(tmp, tag="t"), "glow": lambda: OM.glow_records(tmp),
             "sphere": lambda: sphere_records(tmp)}[name]()
 
@@ -118,7 +123,7 @@ def test_declared_exported_and_bound():
         assert hasattr(raw, name) and hasattr(N.lib(), name)
     dev = re.search(r"ipt_tangent_mat_dev\s*\(([^;]*)\)", header).group(1)
     assert "double *tan_dev" in dev and dev.strip().endswith("void *stream")
-    assert N.lib().ipt_abi_version() == 5 == N.ABI_VERSION
+    assert N.lib().ipt_abi_version() == 6 == N.ABI_VERSION
     assert callable(Scene.tangent_materials) and callable(torch_ops.tangent_materials)
     assert callable(optimize.gauss_newton_materials) and hasattr(torch_ops._MaterialsFn, "jvp")
 

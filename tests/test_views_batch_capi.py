@@ -43,8 +43,8 @@ def refused(scene, handle, text, **kw):
         assert rc == -1 and text in msg, (name, kw, rc, msg)
 
 
-def test_symbols_are_additive_and_the_abi_stays_5():
-    assert N.lib().ipt_abi_version() == 5
+def test_symbols_are_additive_and_the_abi_is_current():
+    assert N.lib().ipt_abi_version() == 6
     assert "ipt_render_views_batch_dev" in N.SIGNATURES and "ipt_adjoint_views_batch_dev" in N.SIGNATURES
 
 
