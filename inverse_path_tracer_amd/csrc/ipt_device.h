@@ -50,15 +50,12 @@ constexpr double kPi = 3.14159265358979323846;
 // < 2^100 -- checked exhaustively for these three b (tools/check_div_const.c,
 // tests/test_identities.py); other x (zeros, tiny, huge, non-finite) take
 // the IEEE division.  Not a generic division: only those three divisors.
-#ifndef IPT_DIV_CONST
-#define IPT_DIV_CONST 1
-#endif
 template <int B>  // 0: kInvPiF, 1: kPRR, 2: kPiF
 __device__ __forceinline__ float div_const(float x) {
   constexpr float b = B == 0 ? kInvPiF : (B == 1 ? kPRR : kPiF);
   constexpr float y = (float)(1.0 / (double)b);
   const float ax = fabsf(x);
-  if (IPT_DIV_CONST && ax >= 0x1p-100f && ax < 0x1p100f) {
+  if (ax >= 0x1p-100f && ax < 0x1p100f) {
     const float q = x * y;
     return fmaf(fmaf(-q, b, x), y, q);
   }
@@ -248,11 +245,7 @@ __device__ __forceinline__ V3 along(V3 p, V3 d, float t) {
 // gives -0 (harmless at both call sites: the hit test rejects t = +-0 by
 // t < eps, the camera's numerator is positive).  Checked on the device by
 // ipt_selftest_math (tests/test_gpu.py).
-#ifndef IPT_FASTDIV
-#define IPT_FASTDIV 1
-#endif
 __device__ __forceinline__ float div_inrange(float a, float b) {
-#if IPT_FASTDIV
   const float nb = -b;
   const float r0 = __builtin_amdgcn_rcpf(b);
   const float e0 = fmaf(nb, r0, 1.0f);
@@ -262,9 +255,6 @@ __device__ __forceinline__ float div_inrange(float a, float b) {
   const float q1 = fmaf(e1, r1, q0);
   const float e2 = fmaf(nb, q1, a);
   return fmaf(e2, r1, q1);
-#else
-  return a / b;
-#endif
 }
 
 // ---- in-range cores of the IEEE sqrt / division lowerings
@@ -384,7 +374,6 @@ __device__ __forceinline__ void pair_ray(const TriPair &T, const PairOrigin &o, 
   const f2 n0 = ld2(T, 3), n1 = ld2(T, 4), n2 = ld2(T, 5);
   const f2 denom = fma2(n2, bc2(d.z), fma2(n1, bc2(d.y), n0 * bc2(d.x)));
   const f2 num = o.num;
-#if IPT_FASTDIV
   // div_inrange(num, -denom), both halves
   const f2 nb = denom;
   const f2 r0 = f2{__builtin_amdgcn_rcpf(-denom.x), __builtin_amdgcn_rcpf(-denom.y)};
@@ -395,9 +384,6 @@ __device__ __forceinline__ void pair_ray(const TriPair &T, const PairOrigin &o, 
   const f2 q1 = fma2(e1, r1, q0);
   const f2 e2 = fma2(nb, q1, num);
   const f2 t = fma2(e2, r1, q1);
-#else
-  const f2 t = f2{num.x / -denom.x, num.y / -denom.y};
-#endif
   const f2 qx = fma2(bc2(d.x), t, bc2(p.x)), qy = fma2(bc2(d.y), t, bc2(p.y)), qz = fma2(bc2(d.z), t, bc2(p.z));
   const f2 s0 = fma2(qz, ld2(T, 8), fma2(qy, ld2(T, 7), fma2(qx, ld2(T, 6), e03)));
   const f2 s1 = fma2(qz, ld2(T, 12), fma2(qy, ld2(T, 11), fma2(qx, ld2(T, 10), e13)));
@@ -431,7 +417,6 @@ __device__ __forceinline__ bool pair_occludes(const TriPair &T, const PairOrigin
   const f2 n0 = ld2(T, 3), n1 = ld2(T, 4), n2 = ld2(T, 5);
   const f2 denom = fma2(n2, bc2(d.z), fma2(n1, bc2(d.y), n0 * bc2(d.x)));
   const f2 num = o.num;
-#if IPT_FASTDIV
   const f2 nb = denom;
   const f2 r0 = f2{__builtin_amdgcn_rcpf(-denom.x), __builtin_amdgcn_rcpf(-denom.y)};
   const f2 e0 = fma2(nb, r0, bc2(1.0f));
@@ -441,9 +426,6 @@ __device__ __forceinline__ bool pair_occludes(const TriPair &T, const PairOrigin
   const f2 q1 = fma2(e1, r1, q0);
   const f2 e2 = fma2(nb, q1, num);
   const f2 t = fma2(e2, r1, q1);  // == div_inrange(num, -denom) per half
-#else
-  const f2 t = f2{num.x / -denom.x, num.y / -denom.y};
-#endif
   const f2 qx = fma2(bc2(d.x), t, bc2(p.x)), qy = fma2(bc2(d.y), t, bc2(p.y)), qz = fma2(bc2(d.z), t, bc2(p.z));
   const f2 s0 = fma2(qz, ld2(T, 8), fma2(qy, ld2(T, 7), fma2(qx, ld2(T, 6), e03)));
   const f2 s1 = fma2(qz, ld2(T, 12), fma2(qy, ld2(T, 11), fma2(qx, ld2(T, 10), e13)));
@@ -479,10 +461,7 @@ __device__ __forceinline__ int closest_hit_pairs_small(const TriPair *__restrict
   // VALU) because a ds_read takes its address from a VGPR.
   typedef __attribute__((address_space(3))) const f2 lds_f2;
   lds_f2 *e3l = (lds_f2 *)e3;
-#ifndef IPT_PIN_E3
-#define IPT_PIN_E3 1
-#endif
-  if (IPT_PIN_E3) asm volatile("" : "+v"(e3l));
+  asm volatile("" : "+v"(e3l));
 #pragma unroll
   for (int j = 0; j < kSmallPairs; ++j) {
     if (j < nP) {  // wave-uniform
@@ -564,7 +543,7 @@ __device__ __forceinline__ void bvh_big_pass(const BvhView &B, V3 p, V3 d, float
   asm volatile("" : "+s"(nP));
   typedef __attribute__((address_space(3))) const f2 lds_f2;  // LDS base pinned in a VGPR (see closest_hit_pairs_small)
   lds_f2 *e3l = (lds_f2 *)B.big_e3;
-  if (IPT_PIN_E3) asm volatile("" : "+v"(e3l));
+  asm volatile("" : "+v"(e3l));
   const cst_i32 *bidx = (const cst_i32 *)B.big_idx;
 #pragma unroll
   for (int j = 0; j < kSmallPairs; ++j) {
@@ -610,15 +589,9 @@ __device__ __forceinline__ SlabRay slab_ray(V3 p, V3 d) {
 // long before t = 1e-2 unless it grazes the wall; all rays of a wave head for
 // the light, so most pairs are skipped for every lane.  A lane is done as
 // soon as the best hit is not the target (occluded).
-#ifndef IPT_SHADOW_CULL
-#define IPT_SHADOW_CULL 1
-#endif
-// IPT_SHADOW_PO=1: the culled shadow cast also skips, per lane, the pairs
-// that cannot occlude any shadow ray from its vertex's triangle to its
-// emitter (static potential-occluder masks, bvh.cpp shadow_occluder_masks)
-#ifndef IPT_SHADOW_PO
-#define IPT_SHADOW_PO 1
-#endif
+// The culled shadow cast also skips, per lane, the pairs that cannot occlude
+// any shadow ray from its vertex's triangle to its emitter (static
+// potential-occluder masks, bvh.cpp shadow_occluder_masks).
 typedef __attribute__((address_space(3))) const uint32_t lds_u32c;
 // Bit j: the ray enters pair j's acceptance box within [kEpsUp, bt] (the
 // pairs' boxes two per PairBox2 record; scalar loads).
@@ -703,45 +676,24 @@ __device__ __forceinline__ TriPair load_pair_lds(const lds_f32 *pl, int j) {
   }
   return T;
 }
-// IPT_SHADOW_PAIR1=1: one evaluation of the target's pair
-// decides the target (its half: hit_test's conditions with bt = inf) and its
-// partner (the other half, under occlusion_pass's bound), instead of
+// The one-pair shadow cast: one evaluation of the target's
+// pair decides the target (its half: hit_test's conditions with bt = inf) and
+// its partner (the other half, under occlusion_pass's bound), instead of
 // hit_test on the target's TriIsect record followed by pair_occludes on the
 // pair that holds it; and the cull setup (slab_ray, box bits, the pair loop)
 // is skipped by the wave when no live lane has another pair to test.
-// 0 keeps the two-step route and its LDS copy of the TriIsect array.
-// IPT_SHADOW_PAIR1_SRC: where the pair comes from.  1: scalar loads of
-// pairs[j] when a ballot shows every lane aims at the same pair (one emitter
-// quad), else per lane, half by half, from the workgroup's LDS copy of the
-// pairs (IPT_PATH_CULL's; global memory without it); 0: always per lane, the
-// whole pair gathered from the LDS copy (36 VGPRs: every brute-force instance
-// then spills).
-#ifndef IPT_SHADOW_PAIR1
-#define IPT_SHADOW_PAIR1 1
-#endif
-#ifndef IPT_PATH_CULL
-#define IPT_PATH_CULL 1
-#endif
-#ifndef IPT_SHADOW_PAIR1_SRC
-#define IPT_SHADOW_PAIR1_SRC 1
-#endif
-#if !IPT_PATH_CULL && !IPT_SHADOW_PAIR1_SRC
-#error "IPT_SHADOW_PAIR1_SRC=0 reads the LDS pair copy that only IPT_PATH_CULL=1 stages"
-#endif
-// LDS floats per triangle of the TriIsect copy (the two-step route's only)
-constexpr int kIsectLdsFloats = IPT_SHADOW_PAIR1 ? 0 : 20;
+// The pair comes in through scalar loads of pairs[j] when a ballot shows every
+// lane aims at the same pair (one emitter quad), else per lane, half by half,
+// from the workgroup's LDS copy of the pairs (the culled path cast's).  A whole
+// pair gathered per lane takes 36 VGPRs: every brute-force instance then
+// spills.
 
 // hit_test's arithmetic on one half of a pair (triangle i = 2j + h is
 // TriPair j's f[k][h]) without the best-t condition: t and "accepts".  The
-// record comes per lane from the workgroup's LDS copy of the pairs, or from
-// global memory when there is none (IPT_PATH_CULL=0).
-__device__ __forceinline__ bool half_test(const lds_f32 *pl, const TriPair *pg, int i, V3 p, V3 d, float &t) {
+// record comes per lane from the workgroup's LDS copy of the pairs.
+__device__ __forceinline__ bool half_test(const lds_f32 *pl, int i, V3 p, V3 d, float &t) {
   float f[18];
-#if IPT_PATH_CULL
   const lds_f32 *q = pl + 36 * (i >> 1) + (i & 1);
-#else
-  const float *q = reinterpret_cast<const float *>(pg) + 36 * (i >> 1) + (i & 1);
-#endif
 #pragma unroll
   for (int k = 0; k < 18; ++k) f[k] = q[2 * k];
   const float denom = fmaf(f[5], d.z, fmaf(f[4], d.y, f[3] * d.x));
@@ -766,7 +718,6 @@ __device__ __forceinline__ bool pair_target(const TriPair &T, const PairOrigin &
   const f2 n0 = ld2(T, 3), n1 = ld2(T, 4), n2 = ld2(T, 5);
   const f2 denom = fma2(n2, bc2(d.z), fma2(n1, bc2(d.y), n0 * bc2(d.x)));
   const f2 num = o.num;
-#if IPT_FASTDIV
   const f2 nb = denom;
   const f2 r0 = f2{__builtin_amdgcn_rcpf(-denom.x), __builtin_amdgcn_rcpf(-denom.y)};
   const f2 e0 = fma2(nb, r0, bc2(1.0f));
@@ -776,9 +727,6 @@ __device__ __forceinline__ bool pair_target(const TriPair &T, const PairOrigin &
   const f2 q1 = fma2(e1, r1, q0);
   const f2 e2 = fma2(nb, q1, num);
   const f2 t = fma2(e2, r1, q1);  // == div_inrange(num, -denom) per half
-#else
-  const f2 t = f2{num.x / -denom.x, num.y / -denom.y};
-#endif
   const f2 qx = fma2(bc2(d.x), t, bc2(p.x)), qy = fma2(bc2(d.y), t, bc2(p.y)), qz = fma2(bc2(d.z), t, bc2(p.z));
   const f2 s0 = fma2(qz, ld2(T, 8), fma2(qy, ld2(T, 7), fma2(qx, ld2(T, 6), e03)));
   const f2 s1 = fma2(qz, ld2(T, 12), fma2(qy, ld2(T, 11), fma2(qx, ld2(T, 10), e13)));
@@ -796,7 +744,6 @@ __device__ __forceinline__ bool pair_target(const TriPair &T, const PairOrigin &
   return hit & !occ;
 }
 
-#if IPT_SHADOW_PAIR1
 // allow_at(): the lane's potential-occluder mask, asked for only after the
 // target's pair is done (one register fewer across that test).
 template <class AllowAt>
@@ -809,7 +756,6 @@ __device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *pairs_lds, 
   const int j = target >> 1, odd = target & 1;
   float te = __builtin_inff();
   bool live = false;
-#if IPT_SHADOW_PAIR1_SRC
   // all lanes aim at one pair (one emitter quad: the common case): it comes
   // in through scalar loads and is evaluated once, packed
   const int js = __builtin_amdgcn_readfirstlane(j);
@@ -820,19 +766,13 @@ __device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *pairs_lds, 
     // mixed pairs in the wave: per lane, the two halves one after the other
     // with hit_test's scalar arithmetic (fewer registers than a gathered pair)
     float tp;
-    const bool vt = half_test(pairs_lds, pairs, 2 * j + odd, p, d, te);
-    const bool vp = half_test(pairs_lds, pairs, 2 * j + (odd ^ 1), p, d, tp);
+    const bool vt = half_test(pairs_lds, 2 * j + odd, p, d, te);
+    const bool vp = half_test(pairs_lds, 2 * j + (odd ^ 1), p, d, tp);
     const bool hit = vt & !(te >= __builtin_inff());
     const float bound = odd ? __uint_as_float(__float_as_uint(te) + 1u) : te;
     live = hit & !(vp & (tp < bound));
     te = hit ? te : __builtin_inff();
   }
-#else
-  {
-    const TriPair T = load_pair_lds(pairs_lds, j);
-    live = pair_target(T, pair_origin(T, p), odd, p, d, e3l[3 * j], e3l[3 * j + 1], e3l[3 * j + 2], te);
-  }
-#endif
   const uint32_t rest = allow_at() & ~(1u << j);  // the target's own pair is done
 #ifdef IPT_BVH_STATS
   atomicAdd(&g_bvh_stats[12], 1ull);                      // shadow lanes
@@ -855,64 +795,15 @@ __device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *pairs_lds, 
     const uint32_t need = live ? pair_box_bits(boxes, nP, p, d, te, rest) : 0u;
     // (the LDS base pinned only now: pinned ahead of the box tests it cost the
     // unbounded adjoint 4 B of scratch per lane)
-    if (IPT_PIN_E3) asm volatile("" : "+v"(e3l));
+    asm volatile("" : "+v"(e3l));
     live = occlusion_pass([&](int k) { return pairs[k]; }, [&](int k) { return k; }, e3l, nP, need, p, d, target, te,
                           live);
   }
   best_t = te;
   return live ? target : -1;
 }
-#else
-// The target's record comes from the workgroup's LDS copy of the TriIsect array.
-template <class AllowAt>
-__device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *isect_lds, const TriPair *__restrict__ pairs,
-                                                      const PairBox2 *__restrict__ boxes, const f2 *e3, int nT, V3 p,
-                                                      V3 d, int target, float &best_t, AllowAt allow_at) {
-  const uint32_t allow = allow_at();
-  float bt = __builtin_inff();
-  int bi = -1;
-  bool live;
-  {
-    TriIsect T;
-    float *tf = reinterpret_cast<float *>(&T);
-    const lds_f32 *q = isect_lds + 20 * target;
-#pragma unroll
-    for (int k = 0; k < 20; ++k) tf[k] = q[k];
-    hit_test(T, target, p, d, bt, bi);
-    live = bi >= 0;
-  }
-  int nP = (nT + 1) >> 1;
-  asm volatile("" : "+s"(nP));
-  lds_f2c *e3l = (lds_f2c *)e3;
-  if (IPT_PIN_E3) asm volatile("" : "+v"(e3l));
-#ifdef IPT_BVH_STATS
-  atomicAdd(&g_bvh_stats[12], 1ull);                      // shadow lanes
-  if (live) atomicAdd(&g_bvh_stats[13], 1ull);            // ... whose target is accepted
-  if (live) atomicAdd(&g_bvh_stats[17], (unsigned long long)nP);  // lane box tests
-  if (__lane_id() == __ffsll((unsigned long long)__builtin_amdgcn_ballot_w64(true)) - 1)
-    atomicAdd(&g_bvh_stats[14], 1ull);                    // wave-level calls
-#endif
-  // opaque per cast: the compiler would otherwise hoist the loop-invariant
-  // box loads out of the megakernel loop into SGPRs, which then spill
-  asm volatile("" : "+s"(boxes));
-  if (__builtin_amdgcn_ballot_w64(live)) {
-    // box bits first, so that the slab registers are dead before the pair tests
-    // the target's own pair is always needed (the ray ends in its box and the
-    // partner may tie ahead of the target): its bit is set without a box test
-    const uint32_t tbit = 1u << (target >> 1);
-    const uint32_t need = live ? (pair_box_bits(boxes, nP, p, d, bt, allow & ~tbit) | tbit) : 0u;
-    live = occlusion_pass([&](int j) { return pairs[j]; }, [&](int k) { return k; }, e3l, nP, need, p, d, target, bt,
-                          live);
-    if (!live && bi >= 0) bi = -1;  // occluded: not the target (the caller only compares with it)
-  }
-  if (!live) bi = -1;
-  best_t = bt;
-  return bi;
-}
-#endif  // IPT_SHADOW_PAIR1
 
-// Path ray of the small-scene loop with per-lane pair culling
-// (IPT_PATH_CULL): a lane tests only the pairs whose acceptance box its ray
+// Path ray of the small-scene loop with per-lane pair culling: a lane tests only the pairs whose acceptance box its ray
 // enters within [kEpsUp, inf) -- no other triangle can accept it (the shadow
 // cull's argument with an unbounded far end) -- in ascending index order with
 // pair_ray's arithmetic and in-order strict accept.  Over a subsequence that
@@ -923,9 +814,6 @@ __device__ __forceinline__ int shadow_hit_pairs_small(const lds_f32 *isect_lds, 
 // per pair: a path ray in a room enters the box of the wall it hits (and, at
 // edges and corners, a neighbour's; crossing an object, its two faces'),
 // whereas the wave's lanes together hit nearly every wall.
-#ifndef IPT_PATH_CULL
-#define IPT_PATH_CULL 1
-#endif
 __device__ __forceinline__ int closest_hit_pairs_culled(const lds_f32 *pairs_lds, const PairBox2 *__restrict__ boxes,
                                                         int nT, V3 p, V3 d, float &best_t) {
   float bt = __builtin_inff();
@@ -997,9 +885,8 @@ __device__ __forceinline__ bool bvh_prepass(const BvhView &B, V3 p, V3 d, float 
   bi = -1;
 #ifdef IPT_BVH_STATS
   atomicAdd(&g_bvh_stats[7], 1ull);
-  if (!(SHADOW && IPT_SHADOW_CULL) && !(!SHADOW && IPT_PATH_CULL && B.big_lds))
-    atomicAdd(&g_bvh_stats[8], 2ull * (unsigned long long)B.nbig);
-  if (SHADOW && IPT_SHADOW_CULL) atomicAdd(&g_bvh_stats[17], (unsigned long long)B.nbig);  // lane box tests
+  if (!SHADOW && !B.big_lds) atomicAdd(&g_bvh_stats[8], 2ull * (unsigned long long)B.nbig);
+  if (SHADOW) atomicAdd(&g_bvh_stats[17], (unsigned long long)B.nbig);  // lane box tests
   if (SHADOW) atomicAdd(&g_bvh_stats[9], 1ull);
 #endif
   if (SHADOW) {
@@ -1020,14 +907,14 @@ __device__ __forceinline__ bool bvh_prepass(const BvhView &B, V3 p, V3 d, float 
       return false;
     }
   }
-  if (SHADOW && IPT_SHADOW_CULL && B.nbig > 0) {
+  if (SHADOW && B.nbig > 0) {
     // the large triangles as in the small scenes' culled shadow cast: only
     // the pairs whose acceptance box some lane's ray enters within
     // [kEpsUp, t_target], reduced to "does it occlude the target"
     int nP = B.nbig;
     asm volatile("" : "+s"(nP));
     lds_f2c *e3l = (lds_f2c *)B.big_e3;
-    if (IPT_PIN_E3) asm volatile("" : "+v"(e3l));
+    asm volatile("" : "+v"(e3l));
     const cst_i32 *bidx = (const cst_i32 *)B.big_idx;
     const PairBox2 *boxes = B.big_boxes;
     asm volatile("" : "+s"(boxes));
@@ -1041,16 +928,10 @@ __device__ __forceinline__ bool bvh_prepass(const BvhView &B, V3 p, V3 d, float 
 #endif
       return false;
     }
-  } else if (!SHADOW && IPT_PATH_CULL && B.big_lds && B.nbig > 0) {
+  } else if (!SHADOW && B.big_lds && B.nbig > 0) {
     bvh_big_pass_culled(B, p, d, bt, bi);
-  } else if (B.nbig > 0) {
-    bvh_big_pass<SHADOW>(B, p, d, bt, bi);
-    if (SHADOW && bi != target) {  // occluded by a large triangle: decided
-#ifdef IPT_BVH_STATS
-      atomicAdd(&g_bvh_stats[10], 1ull);
-#endif
-      return false;
-    }
+  } else if (!SHADOW && B.nbig > 0) {
+    bvh_big_pass<false>(B, p, d, bt, bi);
   }
   return true;
 }
@@ -1207,9 +1088,6 @@ __device__ __forceinline__ float bperm_f(int addr, float v) {
 // that cross the box's corners: a ball fills ~half of a box's mean projected
 // area.  A ray whose origin lies outside it and whose line misses it (or
 // points away from it) accepts no tree triangle.
-#ifndef IPT_TREE_SPHERE
-#define IPT_TREE_SPHERE 1
-#endif
 // The sphere test (b^2 - cc with b = oc.d) and tree_skip's fixed dot margin
 // assume |d| = 1: the megakernel's rays come from unit().  `unit` false (a
 // caller's ray of any length, closest_hit_kernel) keeps the box test only.
@@ -1220,7 +1098,7 @@ __device__ __forceinline__ bool coop_root_test(const CoopView &C, V3 p, V3 d, fl
   const float tz0 = fmaf(C.root[2], r.iz.x, r.oz.x), tz1 = fmaf(C.root[5], r.iz.x, r.oz.x);
   const float en = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), 0.f));
   const float ex = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fminf(fmaxf(tz0, tz1), bt));
-  if (IPT_TREE_SPHERE && unit) {
+  if (unit) {
     const V3 oc = mk(p.x - C.sphere[0], p.y - C.sphere[1], p.z - C.sphere[2]);
     const float b = dot3(oc, d), cc = dot3(oc, oc) - C.sphere[3];
     const bool miss = cc > 0.f && (b > 0.f || fmaf(b, b, -cc) < 0.f);
@@ -1232,9 +1110,6 @@ __device__ __forceinline__ bool coop_root_test(const CoopView &C, V3 p, V3 d, fl
 // triangle s accepted, and dot(n_s, d) >= tau_s puts every tree triangle
 // behind s's plane at every t the hit test accepts.  sc: {n_s, tau_s} per
 // triangle; s < 0 (camera rays): no skip.
-#ifndef IPT_TREE_SKIP
-#define IPT_TREE_SKIP 1
-#endif
 __device__ __forceinline__ bool tree_skip(const float4 *sc, int s, V3 d, bool unit = true) {
   if (s < 0 || !unit) return false;
   const float4 v = sc[s];

@@ -182,12 +182,6 @@ constexpr int kMaxAdjBounces = 62;
 // §10.3).  Round 2 kept an 8-slot ring in LDS (24 KB
 // per workgroup): every path longer than 8 vertices replayed, C3 unbounded
 // adjoint 5.97 ms for a 2.73 ms forward.
-#ifndef IPT_CHAIN_DPP  // the sweep's chain steps with the wave shifts fused into their VALU ops (ipt_device.h)
-#define IPT_CHAIN_DPP 1
-#endif
-#ifndef IPT_ADJU_SHIFTED_CHAIN  // the bounded adjoint's chain form in MODE_ADJU too (A/B)
-#define IPT_ADJU_SHIFTED_CHAIN 0
-#endif
 #ifndef IPT_ADJU_RING
 #define IPT_ADJU_RING 63
 #endif
@@ -224,9 +218,6 @@ constexpr int kPoolSlots = 16, kPoolMaxChunks = 4;
 #ifndef IPT_ADJU_LDS_SLOTS_BVH
 #define IPT_ADJU_LDS_SLOTS_BVH 6
 #endif
-#ifndef IPT_ADJU_LDS_SLOTS_FIXED
-#define IPT_ADJU_LDS_SLOTS_FIXED -1
-#endif
 constexpr int kAdjuRing = IPT_ADJU_RING;
 // Sub-chunked sweep of the unbounded adjoint (IPT_ADJU_SUB = G > 0): a chunk
 // is swept G vertices at a time from its end, one sub-chunk per loop
@@ -247,9 +238,6 @@ constexpr int kMrEnt = kSub > 0 ? (kAdjuRing + kSub - 1) / kSub : 1;
 // north-star 8.52 -> 5.79 ms, adjoints 1.16-1.63x
 // (profiles/r02_variants_dynamic_chunks.log).  IPT_DYN_CHUNKS_PER_WAVE sets
 // the chunk size (items per launch / waves / this, a multiple of 64).
-#ifndef IPT_DYN_CHUNKS
-#define IPT_DYN_CHUNKS 1
-#endif
 #ifndef IPT_DYN_CHUNKS_PER_WAVE
 #define IPT_DYN_CHUNKS_PER_WAVE 32
 #endif
@@ -348,9 +336,10 @@ struct TraceArgs {
   // launch of its own kd and seed
   int nscenes, bps;
   uint64_t seed_stride, out_stride, adj_stride;
-  // dynamic work distribution (IPT_DYN_CHUNKS): a wave starts with chunk
-  // `wave` of `chunk` items and then takes chunk nwaves + atomicAdd(ctr[set])
-  // until the launch's items are used up; chunk 0 = static per-wave ranges
+  // dynamic work distribution: a wave starts with chunk `wave` of `chunk`
+  // items and then takes chunk nwaves + atomicAdd(ctr[set]) until the launch's
+  // items are used up (every launch sets chunk > 0; the kernels still read 0
+  // as static per-wave ranges)
   uint32_t chunk;
   // guided sizes: the first chunk_big_n chunks hold `chunk` units, the rest
   // chunk_small (units: work items, or pixels in MODE_FWDM), so a launch ends
@@ -377,7 +366,7 @@ struct TraceArgs {
   const uint32_t *pomask;
   // BVH scenes: the same masks over the large-triangle pairs (nullptr = none)
   const uint32_t *big_pomask;
-  // FWD with the pixel mean fused in (gpu_render, IPT_FUSED_MEAN): a chunk of
+  // FWD with the pixel mean fused in (gpu_render): a chunk of
   // `chunk` (then chunk_small) launch-local pixels is issued in groups of
   // `group` pixels x spp samples;
   // each pixel of a group gets one of the wave's nslots LDS slots (spp x 3
@@ -531,33 +520,20 @@ __device__ __forceinline__ void item_ray(const TraceArgs &a, uint64_t seed, uint
 // unit() then run once for both groups, and the refill at the loop top is
 // entered only at group boundaries.  With it the pixel part
 // of item_ray_ls is evaluated once per group of pixels, not per sample.
-// 0: the loop as before (make variant, A/B timing).
-#ifndef IPT_INPHASE_REFILL
-#define IPT_INPHASE_REFILL 1
-#endif
-#ifndef IPT_INPHASE_MERGE  // 0: only the per-group pixel entries, refill at the loop top as before (A/B timing)
-#define IPT_INPHASE_MERGE 1
-#endif
-#ifndef IPT_INPHASE_PACK  // 1: the waiting item packed into the item word in the diffuse instances too (A/B timing)
-#define IPT_INPHASE_PACK 0
-#endif
 template <int MODE, bool BVH>
 constexpr bool kInphase() {
-  return IPT_INPHASE_REFILL && MODE == MODE_FWDM && !BVH;
+  return MODE == MODE_FWDM && !BVH;
 }
 // Small scenes' shading data -- normals, sampling frames, Ke, the emitters'
 // vertices, CDF and pmf -- read from the packed LDS records of scene_layout.h
 // instead of per-lane global loads of TriGeom, TriMat and the emitter arrays
-// (trace_shade_kernel).  0: no launch takes them (A/B timing).
-#ifndef IPT_SHADE_TABLES
-#define IPT_SHADE_TABLES 1
-#endif
+// (trace_shade_kernel).
 constexpr int kSmallShade = 2;  // TraceArgs::small_pairs bit 1: the launch carries the shading tables
 // Words per pixel of a group's entry table: seed + pixel * spp (lo, hi),
 // (float)c, (float)r -- item_ray_ls's pixel part; a sample adds its index s.
 constexpr int kEntryWords = 4;
 static inline uint32_t fused_entry_words(uint32_t group, bool bvh) {
-  return (IPT_INPHASE_REFILL && !bvh) ? kEntryWords * group : 0u;
+  return !bvh ? kEntryWords * group : 0u;
 }
 __device__ __forceinline__ void pixel_entry(const TraceArgs &a, uint64_t seed, uint64_t lp, uint32_t e[kEntryWords]) {
   int r, c;
@@ -575,11 +551,6 @@ __device__ __forceinline__ void pixel_entry(const TraceArgs &a, uint64_t seed, u
   e[2] = __float_as_uint((float)c);
   e[3] = __float_as_uint((float)r);
 }
-// Timing-only ablations of the loop-top refill (images are wrong): 1 skips
-// the camera math, 2 the item math too
-#ifndef IPT_REFILL_ABLATE
-#define IPT_REFILL_ABLATE 0
-#endif
 
 // ---------------------------------------------------------------------------
 // Minimum resident 256-thread blocks per CU (= waves per SIMD) requested per
@@ -600,9 +571,6 @@ __device__ __forceinline__ void pixel_entry(const TraceArgs &a, uint64_t seed, u
 #endif
 #ifndef IPT_MIN_BLOCKS_ADJW
 #define IPT_MIN_BLOCKS_ADJW 6
-#endif
-#ifndef IPT_ADJW_LANE_LDS  // MODE_ADJW's work item and Le in LDS (trace_kernel's lane_ws)
-#define IPT_ADJW_LANE_LDS 1
 #endif
 #ifndef IPT_MIN_BLOCKS_GRAPH
 #define IPT_MIN_BLOCKS_GRAPH 0
@@ -677,13 +645,8 @@ constexpr int min_blocks() {
 // rays skip more pair blocks; C2 1.747 -> 1.734 ms, scenes/0 unbounded
 // 3.554 -> 3.502, north star 3.905 -> 3.835, profiles/r06/variants_adj_enumeration_r06t.log)
 // and each pixel's adjoint value is fetched by one chunk, i.e. one XCD's L2
-// (DESIGN.md §12.10).  IPT_ADJ_PIXEL_MAJOR / IPT_GRAPH_PIXEL_MAJOR select it.
-#ifndef IPT_ADJ_PIXEL_MAJOR
-#define IPT_ADJ_PIXEL_MAJOR 1
-#endif
-#ifndef IPT_GRAPH_PIXEL_MAJOR
-#define IPT_GRAPH_PIXEL_MAJOR 1
-#endif
+// (DESIGN.md §12.10).  adjoint_args and gpu_graph clear
+// TraceArgs::sample_major; only the forward's sample buffer sets it.
 #define IPT_TRACE_BOUNDS __attribute__((amdgpu_flat_work_group_size(1, kBlock), amdgpu_waves_per_eu(min_blocks<MODE, BVH>() ? min_blocks<MODE, BVH>() : 1)))
 // Profiling-only build (make variant DEFS=-DIPT_PHASE_TIMING): each wave
 // accumulates s_memtime cycles per phase of the loop; read with
@@ -746,13 +709,13 @@ __host__ __device__ inline size_t emit_lds_bytes(int nE) {
   return nE > 0 && nE <= kEmitLdsMax ? (size_t)nE * sizeof(TriIsect) : 0;
 }
 __host__ __device__ inline size_t big_lds_bytes(int nbig) {
-  return IPT_PATH_CULL && nbig > 0 ? 12 + (size_t)nbig * (sizeof(TriPair) + 2 * sizeof(int32_t)) : 0;
+  return nbig > 0 ? 12 + (size_t)nbig * (sizeof(TriPair) + 2 * sizeof(int32_t)) : 0;
 }
 // Fill that copy at `at` (rounded up to 16 B from the LDS base); returns the
 // first float after it.
 __device__ __forceinline__ float *big_lds_copy(const TraceArgs &a, float *at, float *base, int tid, int nthr,
                                                BvhView &bv) {
-  if (!(IPT_PATH_CULL && a.bvh_nbig > 0 && a.bvh_big_lds)) return at;
+  if (!(a.bvh_nbig > 0 && a.bvh_big_lds)) return at;
   float *pl = at + ((4 - (int)((at - base) & 3)) & 3);
   const float *g = reinterpret_cast<const float *>(a.bvh_big);
   for (int i = tid; i < 36 * a.bvh_nbig; i += nthr) pl[i] = g[i];
@@ -1707,7 +1670,7 @@ static bool use_bvh(const GpuScene *s) {
   return s->host.nT >= kBvhMinTris;
 }
 
-// trace_kernel's lane_ws: six words per lane (the BVH forwards, and MODE_ADJW with IPT_ADJW_LANE_LDS)
+// trace_kernel's lane_ws: six words per lane (the BVH forwards, and MODE_ADJW)
 constexpr size_t kLaneWsBytes = (size_t)6 * kBlock * sizeof(uint32_t);
 
 // BVH LDS carve-out on top of `base` bytes; fills the args' BVH fields:
@@ -1719,8 +1682,8 @@ static size_t bvh_lds(const GpuScene *s, TraceArgs &a, size_t base, bool stage =
   a.bvh_wide = s->wide;
   a.bvh_wtris = s->wtris;
   a.bvh_wide_lds = (stage && nw * kWideF4 * sizeof(float4) <= (size_t)kBvhLdsNodeBytes) ? (int)nw : 0;
-  a.bvh_big_lds = big_copy && IPT_PATH_CULL ? 1 : 0;
-  a.big_pomask = (IPT_SHADOW_PO && s->host.nE > 0 && !s->host.bvh_big_idx.empty()) ? s->big_pomask : nullptr;
+  a.bvh_big_lds = big_copy ? 1 : 0;
+  a.big_pomask = (s->host.nE > 0 && !s->host.bvh_big_idx.empty()) ? s->big_pomask : nullptr;
   a.coop_stride = 7 * s->host.bvh_wdepth + 8;
   a.bvh_nbig = (int)s->host.bvh_big_pairs.size();
   a.bvh_big = s->big_pairs;
@@ -1741,7 +1704,7 @@ static size_t shade_bytes(const TraceArgs &a) {
 // by no other: every size and limit an entry point derives from table_bytes
 // then counts the tables exactly where the launch may carry them.
 static void shade_offer(const GpuScene *s, TraceArgs &a) {
-  if (IPT_SHADE_TABLES && (a.small_pairs & 1) && !use_bvh(s) && shade_tables_fit(s->host.nT, s->host.nE))
+  if ((a.small_pairs & 1) && !use_bvh(s) && shade_tables_fit(s->host.nT, s->host.nE))
     a.small_pairs |= kSmallShade;
 }
 // ... which must not cost a launch a resident workgroup: dropped (bit and
@@ -1754,9 +1717,9 @@ static bool shade_keeps_residency(const TraceArgs &a, size_t lds, size_t extra, 
 
 static size_t table_bytes(const TraceArgs &a) {
   return (a.kd_tables ? (size_t)6 * a.nT * sizeof(float) : 0) +
-         (a.small_pairs ? (size_t)kE3Floats * ((a.nT + 1) / 2) * sizeof(float) + 12 + (size_t)a.nT * kIsectLdsFloats * sizeof(float) +
-                              (IPT_PATH_CULL ? (size_t)((a.nT + 1) / 2) * sizeof(TriPair) : 0) +
-                              (IPT_SHADOW_PO && a.pomask ? (size_t)a.nT * a.nE * sizeof(uint32_t) : 0) +
+         (a.small_pairs ? (size_t)kE3Floats * ((a.nT + 1) / 2) * sizeof(float) + 12 +
+                              (size_t)((a.nT + 1) / 2) * sizeof(TriPair) +
+                              (a.pomask ? (size_t)a.nT * a.nE * sizeof(uint32_t) : 0) +
                               shade_bytes(a)
                         : 0);
 }
@@ -1896,45 +1859,42 @@ static int launch_inst(GpuScene *s, const TraceArgs &a, size_t lds, const Launch
     b.bps = std::max(1, grid / a.nscenes);
     grid = b.bps * a.nscenes;
   }
-  b.chunk = 0;
   b.chunk_ctr = nullptr;
   StreamScratch cap_ctr;  // only for a launch captured into a graph
-  if (IPT_DYN_CHUNKS) {
-    // ~IPT_DYN_CHUNKS_PER_WAVE chunks per wave, a multiple of 64 items, 64..4096
-    const uint64_t waves = (uint64_t)(a.nscenes > 1 ? b.bps : grid) * (kBlock / 64);
-    uint64_t c = (a.n_samples / (waves * IPT_DYN_CHUNKS_PER_WAVE) + 63) / 64 * 64;
-    c = std::min<uint64_t>(std::max<uint64_t>(c, IPT_DYN_MIN_CHUNK), 4096);
-    uint64_t units = a.n_samples, small = std::min<uint64_t>(c, IPT_DYN_SMALL_CHUNK);
-    if (a.fused) {  // fused pixel mean: chunks of a.chunk pixels (all their samples), small ones of >= 64 samples
-      // a launch with fewer chunks than waves (a thin band) halves them while
-      // that gives the idle waves work and a chunk keeps >= 64 samples: C2's
-      // 1/64 share 0.217 -> 0.10 ms (profiles/r03/launch_scaling_r03w.jsonl)
-      c = a.chunk;
-      while (c > 1 && (a.npix + c - 1) / c < waves && (c / 2) * (uint64_t)a.spp >= 64) c /= 2;
-      b.group = std::min<uint32_t>(a.group, (uint32_t)c);
-      small = std::min<uint64_t>(c, std::max<uint64_t>(1, 64 / (uint64_t)a.spp));
-      units = a.npix;
-    }
-    // guided sizes: the last ~IPT_GUIDED_TAIL small chunks per wave end the launch
-    // (non-guided instances: one size, chunk_small = chunk and no big-chunk count;
-    // IPT_BF_BIG > 1: big chunks of IPT_BF_BIG x c, then IPT_BF_TAIL chunks of
-    // c per wave -- fewer grabs for the same tail)
-    if (!BVH) {
-      small = c;
-      c *= IPT_BF_BIG;
-    }
-    b.chunk = (uint32_t)c;
-    b.chunk_small = (uint32_t)small;
-    const uint64_t rw = waves;  // chunks 0 .. rw-1: the waves' own; every wave ends with one failed grab
-    constexpr bool guided = kGuided<BVH>();
-    const uint64_t tail = guided ? rw * (uint64_t)(BVH ? IPT_GUIDED_TAIL : IPT_BF_TAIL) * small : 0;
-    const uint64_t nb = guided ? (units > tail ? (units - tail) / c : 0) : 0;
-    b.chunk_big_n = (uint32_t)nb;
-    b.grabs = launch_grabs(guided, units, c, small, nb, rw);
-    cap_ctr.st = st;
-    const int words = a.nscenes * kCtrStride;
-    if (stream_counters(s, st, words, &b.chunk_ctr, &cap_ctr.p)) return -1;
+  // ~IPT_DYN_CHUNKS_PER_WAVE chunks per wave, a multiple of 64 items, 64..4096
+  const uint64_t waves = (uint64_t)(a.nscenes > 1 ? b.bps : grid) * (kBlock / 64);
+  uint64_t c = (a.n_samples / (waves * IPT_DYN_CHUNKS_PER_WAVE) + 63) / 64 * 64;
+  c = std::min<uint64_t>(std::max<uint64_t>(c, IPT_DYN_MIN_CHUNK), 4096);
+  uint64_t units = a.n_samples, small = std::min<uint64_t>(c, IPT_DYN_SMALL_CHUNK);
+  if (a.fused) {  // fused pixel mean: chunks of a.chunk pixels (all their samples), small ones of >= 64 samples
+    // a launch with fewer chunks than waves (a thin band) halves them while
+    // that gives the idle waves work and a chunk keeps >= 64 samples: C2's
+    // 1/64 share 0.217 -> 0.10 ms (profiles/r03/launch_scaling_r03w.jsonl)
+    c = a.chunk;
+    while (c > 1 && (a.npix + c - 1) / c < waves && (c / 2) * (uint64_t)a.spp >= 64) c /= 2;
+    b.group = std::min<uint32_t>(a.group, (uint32_t)c);
+    small = std::min<uint64_t>(c, std::max<uint64_t>(1, 64 / (uint64_t)a.spp));
+    units = a.npix;
   }
+  // guided sizes: the last ~IPT_GUIDED_TAIL small chunks per wave end the launch
+  // (non-guided instances: one size, chunk_small = chunk and no big-chunk count;
+  // IPT_BF_BIG > 1: big chunks of IPT_BF_BIG x c, then IPT_BF_TAIL chunks of
+  // c per wave -- fewer grabs for the same tail)
+  if (!BVH) {
+    small = c;
+    c *= IPT_BF_BIG;
+  }
+  b.chunk = (uint32_t)c;
+  b.chunk_small = (uint32_t)small;
+  const uint64_t rw = waves;  // chunks 0 .. rw-1: the waves' own; every wave ends with one failed grab
+  constexpr bool guided = kGuided<BVH>();
+  const uint64_t tail = guided ? rw * (uint64_t)(BVH ? IPT_GUIDED_TAIL : IPT_BF_TAIL) * small : 0;
+  const uint64_t nb = guided ? (units > tail ? (units - tail) / c : 0) : 0;
+  b.chunk_big_n = (uint32_t)nb;
+  b.grabs = launch_grabs(guided, units, c, small, nb, rw);
+  cap_ctr.st = st;
+  const int words = a.nscenes * kCtrStride;
+  if (stream_counters(s, st, words, &b.chunk_ctr, &cap_ctr.p)) return -1;
   StreamScratch grec, mring;  // ADJU: the vertex-record ring (TraceArgs::grec), freed behind the launch
   if (MODE == MODE_ADJU) {  // the ring's global slots: one chunk pool per wave
     const size_t fields = SPEC ? kRecFieldsSpec : kRecFieldsDiffuse;
@@ -2148,7 +2108,7 @@ int gpu_pixel_mean_sm(const float *samples_dev, int64_t npix, int spp, float *hd
   return pixel_mean_sm_sets(samples_dev, npix, spp, 1, hdr_dev, ldr_dev, stream);
 }
 
-// Fused pixel mean (IPT_FUSED_MEAN): the ring of one-pixel slots per wave
+// Fused pixel mean: the ring of one-pixel slots per wave
 // (nslots, <= 16, spp x 3 floats each, IPT_FUSED_WAVE_BYTES of LDS per wave)
 // and the pixels per group (a power of two, group x spp <= 256 samples, >= 32),
 // or {0, 0} when the launch renders through the sample
@@ -2158,11 +2118,7 @@ int gpu_pixel_mean_sm(const float *samples_dev, int64_t npix, int spp, float *hd
 // still leave the next groups their slots -- simulated lane use >= 99% for
 // the reference's Russian roulette).  The index math needs
 // < 2^32 samples per frame.  (The unfused path stays reachable through
-// ipt_render_samples_sm_dev + ipt_pixel_mean_sm_dev; `make variant
-// DEFS=-DIPT_FUSED_MEAN=0` builds a library without the fused render.)
-#ifndef IPT_FUSED_MEAN
-#define IPT_FUSED_MEAN 1
-#endif
+// ipt_render_samples_sm_dev + ipt_pixel_mean_sm_dev.)
 #ifndef IPT_FUSED_GRAB_SAMPLES  // samples handed out per counter grab (at least)
 #define IPT_FUSED_GRAB_SAMPLES 256
 #endif
@@ -2185,7 +2141,6 @@ struct FusedShape {
 #endif
 static FusedShape fused_shape(const RenderParams &p, bool bvh) {
   const FusedShape none = {0, 0, 0};
-  if (!IPT_FUSED_MEAN || !IPT_DYN_CHUNKS) return none;
   if ((uint64_t)p.width * (uint64_t)p.height * (uint64_t)p.spp > 0xffffffffull || p.spp > 256) return none;
   int bytes = IPT_FUSED_WAVE_BYTES;
   if (bvh) {
@@ -2356,12 +2311,12 @@ int gpu_render_mat_batch(GpuScene *s, const RenderParams &p, const float *kd_dev
 }
 
 // ------------------------------------------------------------ adjoints
-// The args of every adjoint launch: make_args, the image order of
-// IPT_ADJ_PIXEL_MAJOR, and the gradient bins (all triangles in LDS, or the
+// The args of every adjoint launch: make_args, the pixel-major work order
+// (DESIGN.md §12.10), and the gradient bins (all triangles in LDS, or the
 // hot set of gpu_upload's grad_map).
 static TraceArgs adjoint_args(const GpuScene *s, const RenderParams &p) {
   TraceArgs a = make_args(s, p);
-  a.sample_major = IPT_ADJ_PIXEL_MAJOR ? 0 : 1;  // (see IPT_ADJ_PIXEL_MAJOR)
+  a.sample_major = 0;
   if (s->grad_map) {
     a.grad_slots = kLdsGradBytes / (3 * (int)sizeof(double));
     a.grad_map = s->grad_map;
@@ -2376,8 +2331,7 @@ static TraceArgs adjoint_args(const GpuScene *s, const RenderParams &p) {
 // whose LDS is `base` bytes plus `per` bytes per ring slot: up to
 // IPT_ADJU_LDS_SLOTS (brute force) or IPT_ADJU_LDS_SLOTS_BVH slots, as many
 // as cost no resident workgroup (searched for the brute-force instances and
-// cached per scene for this base in *cached_base / *cached_nl; a variant
-// built with IPT_ADJU_LDS_SLOTS_FIXED >= 0 fixes the count, A/B timing); the
+// cached per scene for this base in *cached_base / *cached_nl); the
 // rest of the ring lives in global memory (launch_inst sizes that part).
 // At least 1: a lane's first record never waits for a pool chunk -- with none
 // left it could not start its ring -- so a scene whose base leaves no room
@@ -2387,9 +2341,7 @@ template <int KIND>
 static int ring_lds_slots(GpuScene *s, size_t base, size_t per, bool bvh, size_t *cached_base, int *cached_nl,
                           int *rec_lds) {
   int nl = bvh ? IPT_ADJU_LDS_SLOTS_BVH : IPT_ADJU_LDS_SLOTS;
-  if (IPT_ADJU_LDS_SLOTS_FIXED >= 0) {
-    nl = IPT_ADJU_LDS_SLOTS_FIXED;
-  } else if (!bvh) {
+  if (!bvh) {
     if (*cached_base != base) {
       auto occ = [&](size_t bytes, int *o) {
         return s->has_ks ? hipOccupancyMaxActiveBlocksPerMultiprocessor(o, kernel_of<MODE_ADJU, true, false, KIND>(), kBlock, bytes)
@@ -2932,7 +2884,7 @@ int gpu_adjoint(GpuScene *s, const RenderParams &p, const float *kd_dev, const f
   if (unbounded) return launch<MODE_ADJU>(s, a, lds, io);
   // the 6-wave instance for full-size launches whose LDS leaves room for a
   // sixth workgroup per CU (IPT_ADJW=0/1 in the environment forces the choice)
-  const size_t lane_words = IPT_ADJW_LANE_LDS ? kLaneWsBytes : 0;
+  const size_t lane_words = kLaneWsBytes;  // MODE_ADJW's work item and Le in LDS (trace_kernel's lane_ws)
   bool wide = !use_bvh(s) && !s->has_ks && 6 * (lds + lane_words) <= 160 * 1024 &&
               (uint64_t)a.n_samples * (uint64_t)std::max(1, a.nscenes) >= IPT_ADJW_MIN_SAMPLES;
   if (const char *e = std::getenv("IPT_ADJW")) wide = std::atoi(e) != 0 && !use_bvh(s) && !s->has_ks;
@@ -2950,7 +2902,7 @@ int gpu_graph(GpuScene *s, const RenderParams &p, const uint8_t *target_dev, dou
   const size_t bins = graph_lds_doubles(s->host.nT, s->host.nE) * sizeof(double);
   a.lds_edges = bins <= (size_t)IPT_GRAPH_LDS_KB * 1024 ? 1 : 0;
   a.kd_tables = 0;  // the graph integrator never reads albedo
-  a.sample_major = IPT_GRAPH_PIXEL_MAJOR ? 0 : 1;  // (see IPT_ADJ_PIXEL_MAJOR)
+  a.sample_major = 0;  // pixel-major, as the adjoints (adjoint_args)
   LaunchIO io;
   io.target = target_dev, io.edges = acc_dev, io.stream = (hipStream_t)stream;
   return launch<MODE_GRAPH>(s, a, (a.lds_edges ? bins : 0) + table_bytes(a), io);
@@ -3103,17 +3055,11 @@ __global__ __launch_bounds__(kBlock) void closest_hit_kernel(const TriIsect *__r
     for (int i = tid; i < kE3Floats * nP; i += kBlock) lds_e3[i] = small_table_entry(pairs, i);
     e3 = reinterpret_cast<const f2 *>(lds_e3);
   }
-  // the two-step shadow cast's LDS copy of the TriIsect records (!BVH, small, IPT_SHADOW_PAIR1=0)
-  float *lds_is = lds_e3 + kE3Floats * nP;
-  lds_is += (4 - (int)((lds_is - lds_e3) & 3)) & 3;
-  float *lds_pr = lds_is + kIsectLdsFloats * nT;  // the culled path cast's TriPair copy (!BVH, small)
+  float *lds_pr = lds_e3 + kE3Floats * nP;  // the culled path cast's TriPair copy (!BVH, small), 16-B aligned
+  lds_pr += (4 - (int)((lds_pr - lds_e3) & 3)) & 3;
   if (!BVH && small) {
-    const float *g = reinterpret_cast<const float *>(isect);
-    for (int i = tid; i < kIsectLdsFloats * nT; i += kBlock) lds_is[i] = g[i];
-    if (IPT_PATH_CULL) {
-      const float *gp = reinterpret_cast<const float *>(pairs);
-      for (int i = tid; i < 36 * nP; i += kBlock) lds_pr[i] = gp[i];
-    }
+    const float *gp = reinterpret_cast<const float *>(pairs);
+    for (int i = tid; i < 36 * nP; i += kBlock) lds_pr[i] = gp[i];
   }
   BvhView bv;
   bv.isect = isect;
@@ -3176,23 +3122,23 @@ __global__ __launch_bounds__(kBlock) void closest_hit_kernel(const TriIsect *__r
       // only, so the BVH answers the brute-force loop for any direction
       const bool unit = fabsf(dot3(d, d) - 1.f) <= 0x1p-20f;
       if (target >= 0) {
-        const uint32_t allow = probe_allow(IPT_SHADOW_PO ? a.big_pomask : nullptr, emit_tri, a.nE, nT, src, target);
+        const uint32_t allow = probe_allow(a.big_pomask, emit_tri, a.nE, nT, src, target);
         if (bvh_prepass<true>(bv, p, d, t, h, target, allow))
-          qn = coop_root_test(cv, p, d, t, unit) && !(IPT_TREE_SKIP && tree_skip(a.src_cull, src, d, unit));
+          qn = coop_root_test(cv, p, d, t, unit) && !tree_skip(a.src_cull, src, d, unit);
       } else {  // (a path ray with a source: the megakernel's bounce ray leaving that triangle)
         bvh_prepass<false>(bv, p, d, t, h, -1);
-        qn = coop_root_test(cv, p, d, t, unit) && !(IPT_TREE_SKIP && tree_skip(a.src_cull, src, d, unit));
+        qn = coop_root_test(cv, p, d, t, unit) && !tree_skip(a.src_cull, src, d, unit);
       }
     }
     coop_cast<false>(cv, qn && target < 0, p, d, t, h);
     coop_cast<true>(cv, qn && target >= 0, p, d, t, h);
   } else if (valid) {
-    if (IPT_SHADOW_CULL && small && target >= 0) {  // the megakernel's shadow cast of small scenes
-      h = shadow_hit_pairs_small((const lds_f32 *)(IPT_SHADOW_PAIR1 ? lds_pr : lds_is), pairs, a.pboxes, e3, nT, p, d,
+    if (small && target >= 0) {  // the megakernel's shadow cast of small scenes
+      h = shadow_hit_pairs_small((const lds_f32 *)lds_pr, pairs, a.pboxes, e3, nT, p, d,
                                  target, t, [&]() {
-                                   return probe_allow(IPT_SHADOW_PO ? a.pomask : nullptr, emit_tri, a.nE, nT, src, target);
+                                   return probe_allow(a.pomask, emit_tri, a.nE, nT, src, target);
                                  });
-    } else if (IPT_PATH_CULL && small && targets && target < 0) {  // ... and its path cast
+    } else if (small && targets && target < 0) {  // ... and its path cast
       h = closest_hit_pairs_culled((const lds_f32 *)lds_pr, a.pboxes, nT, p, d, t);
     } else {  // the full closest hit (brute-force pair loop)
       h = cast_bf(pairs, e3, nT, p, d, t);
@@ -3234,9 +3180,7 @@ int gpu_closest_hit(GpuScene *s, int64_t n, const float *org_dev, const float *d
     hipLaunchKernelGGL(closest_hit_kernel<true>, dim3(blocks), dim3(kBlock), lds, (hipStream_t)stream, s->isect,
                        s->pairs, a, small, n, org_dev, dir_dev, targets_dev, sources_dev, s->emit_tri, t_dev, idx_dev);
   } else {
-    const size_t lds = base + (small ? 12 + (size_t)s->host.nT * kIsectLdsFloats * sizeof(float) +
-                                           (IPT_PATH_CULL ? (size_t)((s->host.nT + 1) / 2) * sizeof(TriPair) : 0)
-                                     : 0);
+    const size_t lds = base + (small ? 12 + (size_t)((s->host.nT + 1) / 2) * sizeof(TriPair) : 0);
     hipLaunchKernelGGL(closest_hit_kernel<false>, dim3(blocks), dim3(kBlock), lds, (hipStream_t)stream, s->isect,
                        s->pairs, a, small, n, org_dev, dir_dev, targets_dev, sources_dev, s->emit_tri, t_dev, idx_dev);
   }

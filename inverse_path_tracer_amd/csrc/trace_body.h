@@ -114,24 +114,17 @@
     for (int i = tid; i < kE3Floats * nP; i += nthr) lds_e3[i] = small_table_entry(pairs, i);
     e3 = reinterpret_cast<const f2 *>(lds_e3);
   }
-  // small scenes, two-step shadow cast only (IPT_SHADOW_PAIR1=0): a copy of
-  // the TriIsect records (16-B aligned), read by its per-lane target test
-  float *lds_is = lds_e3 + (a.small_pairs ? kE3Floats * nP : 0);
-  lds_is += (4 - (int)((lds_is - reinterpret_cast<float *>(lds)) & 3)) & 3;
-  if (kIsectLdsFloats != 0 && a.small_pairs) {
-    const float *g = reinterpret_cast<const float *>(isect);
-    for (int i = tid; i < kIsectLdsFloats * nT; i += nthr) lds_is[i] = g[i];
-  }
-  // small scenes, culled path cast (IPT_PATH_CULL): a copy of the TriPair
-  // records (16-B aligned), gathered per lane
-  float *lds_pr = lds_is + (a.small_pairs ? kIsectLdsFloats * nT : 0);
-  if (a.small_pairs && IPT_PATH_CULL) {
+  // small scenes, culled path cast: a copy of the TriPair records (16-B
+  // aligned), gathered per lane
+  float *const e3_end = lds_e3 + (a.small_pairs ? kE3Floats * nP : 0);
+  float *lds_pr = e3_end + ((4 - (int)((e3_end - reinterpret_cast<float *>(lds)) & 3)) & 3);
+  if (a.small_pairs) {
     const float *g = reinterpret_cast<const float *>(pairs);
     for (int i = tid; i < 36 * nP; i += nthr) lds_pr[i] = g[i];
   }
-  // ... and the shadow casts' potential-occluder masks (IPT_SHADOW_PO)
-  uint32_t *lds_po = reinterpret_cast<uint32_t *>(lds_pr + (a.small_pairs && IPT_PATH_CULL ? 36 * nP : 0));
-  const bool po = a.small_pairs && IPT_SHADOW_PO && a.pomask;
+  // ... and the shadow casts' potential-occluder masks
+  uint32_t *lds_po = reinterpret_cast<uint32_t *>(lds_pr + (a.small_pairs ? 36 * nP : 0));
+  const bool po = a.small_pairs && a.pomask;
   if (po)
     for (int i = tid; i < nT * nE; i += nthr) lds_po[i] = a.pomask[i];
   if (SHADE) {  // the shading tables' fill
@@ -192,8 +185,8 @@
   // The 6-wave adjoint (MODE_ADJW, 80 VGPRs) likewise keeps its work item
   // and Le there (its path source is not needed): in registers they pushed
   // the culled path cast past 80 VGPRs and a ray-direction pair was reloaded
-  // from scratch in every pair block (16 B/lane of scratch; IPT_ADJW_LANE_LDS)
-  constexpr bool kLaneLds = (BVH && is_fwd<MODE>()) || (!BVH && MODE == MODE_ADJW && IPT_ADJW_LANE_LDS);
+  // from scratch in every pair block (16 B/lane of scratch)
+  constexpr bool kLaneLds = (BVH && is_fwd<MODE>()) || (!BVH && MODE == MODE_ADJW);
   lds_u32 *lane_ws = nullptr;
   if (!BVH && kLaneLds)  // after the vertex records ([6][kBlock] words, as the BVH forward's)
     lane_ws = (lds_u32 *)(lds_rec + (size_t)vmax * kRecFieldsDiffuse * kBlock);
@@ -438,11 +431,11 @@
   // (VIEWS: the merged block rotates camera rays by record nT of geom, the
   // SCENE's camera -- the view instances keep the entries and refill at the
   // loop top from the view's own matrix; same frames, §17.2)
-  constexpr bool kInphM = kInph && IPT_INPHASE_MERGE && !VIEWS;  // 0: the entries only (A/B timing)
+  constexpr bool kInphM = kInph && !VIEWS;
   // kInphP: the sample taken in phase waits above the old path's item in the
   // one item word; else in a register of its own.  The SPEC instances spill
   // 16 B per lane with the register, the diffuse ones are 0.5% slower packed.
-  constexpr bool kInphP = kInphM && (SPEC || IPT_INPHASE_PACK);
+  constexpr bool kInphP = kInphM && SPEC;
   auto fused_tab = [&](const TraceArgs &A) -> lds_u32 * {
     return (lds_u32 *)(reinterpret_cast<char *>(lds) + A.mean_off) + (size_t)(tid >> 6) * A.mean_wstride;
   };
@@ -630,22 +623,7 @@
           const uint32_t j = fj + rank;
           const uint32_t s = (gnp & (gnp - 1u)) == 0u ? j >> __builtin_ctz(gnp) : j / gnp;
           const uint32_t q = j - s * gnp;
-          if (IPT_REFILL_ABLATE && !BVH) {  // timing only: no camera math (1), no item math either (2, 3)
-            uint64_t g = (uint64_t)(glp * (uint32_t)a.spp + j);
-            if (IPT_REFILL_ABLATE < 2) {
-              int r, c;
-              local_rc(a, glp + q, r, c);
-              g = (uint64_t)((uint32_t)r * (uint32_t)a.W + (uint32_t)c) * (uint32_t)a.spp + s;
-            }
-            rng_init(st, seed + g);
-            p = mk(a.cam_org[0], a.cam_org[1], a.cam_org[2]);
-            d = mk(a.cam[2], a.cam[6], a.cam[10]);  // the view axis: a unit vector into the scene
-            if (IPT_REFILL_ABLATE == 3) {  // the paths' statistics kept: the pixel's direction, neither rotated nor unit
-              const float u0 = uniform(st), u1 = uniform(st);
-              d = mk(2.f * ((float)((glp + q) & 511u) + u0) * a.rc_W - 1.f,
-                     1.f - 2.f * ((float)((glp + q) >> 9) + u1) * a.rc_H, 1.f);  // (a 512-wide frame)
-            }
-          } else if (kInph) {
+          if (kInph) {
             float cf, rf;
             rng_init(st, entry_sample(a, q, s, cf, rf));
             camera_ray_f(a.cam, a.cam_org, st, rf, cf, a.W, a.H, a.rc_W, a.rc_H, p, d);
@@ -717,13 +695,13 @@
       bool qn = false;
       if (active) {
         bvh_prepass<false>(bv, p, d, t, hit, -1);
-        qn = coop_root_test(cv, p, d, t) && !(IPT_TREE_SKIP && tree_skip(a.src_cull, ptri(), d));
+        qn = coop_root_test(cv, p, d, t) && !tree_skip(a.src_cull, ptri(), d);
       }
       SUBPHASE_BEGIN
       coop_cast<false>(cv, qn, p, d, t, hit);
       SUBPHASE_END(8)
     } else if (active) {
-      if (IPT_PATH_CULL && e3)
+      if (e3)
         hit = closest_hit_pairs_culled((const lds_f32 *)lds_pr, a.pboxes, nT, p, d, t);
       else
         hit = cast_bf(pairs, e3, nT, p, d, t);
@@ -971,13 +949,13 @@
         bool qn = false;
         if (shadow && bvh_prepass<true>(bv, p, sd, ts, hs, et,
                                         a.big_pomask ? a.big_pomask[tri * nE + emitter] : 0xffffffffu, emitter))
-          qn = coop_root_test(cv, p, sd, ts) && !(IPT_TREE_SKIP && tree_skip(a.src_cull, tri, sd));
+          qn = coop_root_test(cv, p, sd, ts) && !tree_skip(a.src_cull, tri, sd);
         SUBPHASE_BEGIN
         coop_cast<true>(cv, qn, p, sd, ts, hs);
         SUBPHASE_END(9)
       } else if (shadow) {
-        if (IPT_SHADOW_CULL && e3)
-          hs = shadow_hit_pairs_small((const lds_f32 *)(IPT_SHADOW_PAIR1 ? lds_pr : lds_is), pairs, a.pboxes, e3, nT, p, sd, et, ts,
+        if (e3)
+          hs = shadow_hit_pairs_small((const lds_f32 *)lds_pr, pairs, a.pboxes, e3, nT, p, sd, et, ts,
                                       [&]() { return po ? ((const lds_u32c *)lds_po)[tri * nE + emitter] : 0xffffffffu; });
         else
           hs = cast_bf(pairs, e3, nT, p, sd, ts);
@@ -1437,51 +1415,20 @@
             // per-step compares and one shift fewer per channel.)
             float mx = Mk.x, my = Mk.y, mz = Mk.z, sx = S.x, sy = S.y, sz = S.z;
             int s = 1;
-            if (is_badj<MODE>() || IPT_ADJU_SHIFTED_CHAIN) {
+            if (is_badj<MODE>()) {
               const V3 tvl = mk(wave_shr1(tv.x), wave_shr1(tv.y), wave_shr1(tv.z));
               const float ckl = wave_shr1(ck);
               const V3 Al = mk(wave_shl1(A.x), wave_shl1(A.y), wave_shl1(A.z));
               const V3 Bl = mk(wave_shl1(B.x), wave_shl1(B.y), wave_shl1(B.z));
               const bool keepM = kkp == 0, keepS = rr == 0;
-#if IPT_CHAIN_DPP
               const uint64_t kM = __ballot(keepM), kS = __ballot(keepS);
               do {
                 chain_step_shifted(mx, my, mz, sx, sy, sz, tvl, ckl, Al, Bl, kM, kS);
               } while (__ballot(steps > s++));
-#else
-              do {  // (a do-while: the loop-carried values need no copies per step)
-                const float nx = (wave_shr1(mx) * tvl.x) * ckl, ny = (wave_shr1(my) * tvl.y) * ckl,
-                            nz = (wave_shr1(mz) * tvl.z) * ckl;
-                const float hx = Al.x + Bl.x * wave_shl1(sx), hy = Al.y + Bl.y * wave_shl1(sy),
-                            hz = Al.z + Bl.z * wave_shl1(sz);
-                mx = keepM ? mx : nx;
-                my = keepM ? my : ny;
-                mz = keepM ? mz : nz;
-                sx = keepS ? sx : hx;
-                sy = keepS ? sy : hy;
-                sz = keepS ? sz : hz;
-              } while (__ballot(steps > s++));
-#endif
             } else {  // ADJU (register pressure: no pre-shifted operands; a lane takes its neighbour's value at step kk / rr)
-#if IPT_CHAIN_DPP
               do {
                 chain_step_select(mx, my, mz, sx, sy, sz, tv, ck, A, B, kkp, rr, s);
               } while (__ballot(steps > s++));
-#else
-              do {
-                const float nx = wave_shr1((mx * tv.x) * ck), ny = wave_shr1((my * tv.y) * ck),
-                            nz = wave_shr1((mz * tv.z) * ck);
-                const float hx = wave_shl1(A.x + B.x * sx), hy = wave_shl1(A.y + B.y * sy),
-                            hz = wave_shl1(A.z + B.z * sz);
-                const bool tm = kkp == s, ts = rr == s;
-                mx = tm ? nx : mx;
-                my = tm ? ny : my;
-                mz = tm ? nz : mz;
-                sx = ts ? hx : sx;
-                sy = ts ? hy : sy;
-                sz = ts ? hz : sz;
-              } while (__ballot(steps > s++));
-#endif
             }
             Mk = mk(mx, my, mz);
             S = mk(sx, sy, sz);

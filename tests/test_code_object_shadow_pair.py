@@ -1,4 +1,4 @@
-"""The one-pair shadow cast (ipt_device.h, IPT_SHADOW_PAIR1) must
+"""The one-pair shadow cast (ipt_device.h, shadow_hit_pairs_small) must
 not cost the C2 headline's kernels registers or occupancy (no GPU needed): the
 fused render trace_kernel<4, false, false> stays at <= 96 VGPRs (5 waves/SIMD)
 without scratch, the 6-wave adjoint trace_kernel<5, false, false> at <= 80

@@ -1,5 +1,5 @@
 """The small scenes' shadow cast decides target and partner with one evaluation
-of the target's pair (ipt_device.h, IPT_SHADOW_PAIR1) and skips
+of the target's pair (ipt_device.h, shadow_hit_pairs_small) and skips
 the cull when no other pair can occlude (run with -m gpu).
 
 Every case sends about 1e5 rays through the probes and compares the culled

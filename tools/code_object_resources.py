@@ -3,11 +3,17 @@
 notes -- no GPU needed:
 
     python tools/code_object_resources.py [LIB] > resources.json
+    python tools/code_object_resources.py --sections [LIB]
+
+The second form prints the digests of the sections that hold the machine code
+(see sections()), for comparing two builds.  LIB may also be a device-only
+object (`hipcc --cuda-device-only -c`).
 
 For each kernel: VGPRs, SGPRs, VGPR/SGPR spill counts, scratch bytes per
 lane (private_segment_fixed_size) and the LDS it declares statically.
 tests/test_code_object.py holds the budgets of the shipping instances.
 """
+import hashlib
 import json
 import os
 import re
@@ -72,7 +78,33 @@ def resources(lib=None):
     return out
 
 
+def sections(lib=None):
+    """SHA-256 of the code object's .text, .rodata and .note, and its symbol
+    names without the per-build `__hip_cuid_<hash>`: two builds with equal
+    digests and equal names hold the same machine code, kernel descriptors and
+    kernel metadata."""
+    lib = lib or os.path.join(ROOT, "inverse_path_tracer_amd", "lib", "libipt_amd.so")
+    elf = gfx950_object(lib)
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
+    hdrs = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]
+    body = lambda h: elf[h[4]:h[4] + h[5]]
+    cstr = lambda tab, at: tab[at:tab.index(b"\0", at)].decode()
+    names = body(hdrs[shstrndx])
+    by_name = {cstr(names, h[0]): h for h in hdrs}
+    out = {name: {"bytes": by_name[name][5], "sha256": hashlib.sha256(body(by_name[name])).hexdigest()}
+           for name in (".text", ".rodata", ".note")}
+    symtab, strtab = body(by_name[".symtab"]), body(by_name[".strtab"])
+    syms = sorted({cstr(strtab, struct.unpack_from("<I", symtab, at)[0]) for at in range(0, len(symtab), 24)} - {""})
+    syms = [s for s in syms if not s.startswith("__hip_cuid_")]
+    out["symbols"] = {"count": len(syms), "sha256": hashlib.sha256("\n".join(syms).encode()).hexdigest()}
+    return out
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--sections":
+        print(json.dumps(sections(sys.argv[2] if len(sys.argv) > 2 else None), indent=1))
+        sys.exit(0)
     r = resources(sys.argv[1] if len(sys.argv) > 1 else None)
     print(json.dumps({"source": "code object metadata (llvm-readelf --notes) of the built library",
                       "note": "trace_kernel<MODE,SPEC,BVH>: MODE 0 FWD, 1 ADJ, 2 GRAPH, 3 ADJU, 4 FWDM",
